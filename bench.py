@@ -11,18 +11,29 @@ Workload at N=1: BASELINE.json configs[1], 8 GiB int32 (2^31 elements, bytesofty
 codec only), variant (b) of SURVEY.md section 8d: uniform 12-bit values `u & 0xFFF` from splitmix64 seed 42
 -- the variant in which the codec does real work (ratio ~2.52).  The literal full-entropy variant (a),
 where every superblock falls back to COPY, is measured too and reported under "full_entropy" with a roofline of
-its own.  --config int16 / double run one shard of configs[3] / configs[2] at level 1 the same way.
+its own (--full).  --config int16 / double run one shard of configs[3] / configs[2] at level 1 the same way.
 With --gpus N every rank owns its own 8 GiB superblock range of an 8*N GiB array (weak scaling, no
-data-path collective in the timed region); the gather of the compressed segments to rank 0 and the sharded
+data-path collective in the timed region); with --full the gather of the compressed segments to rank 0 and the sharded
 decode are run and timed afterwards ("sharded_exchange").
-Outside the timed region at N=1: the reference's CPU path on a 1 GiB prefix ("cpu_baseline"), a byte-for-byte
-comparison of the WHOLE GPU frame with the reference's frames of its 1 GiB slices ("parity_bytes"), the host-pointer
-ABI end to end ("host_pointer"), the other configurations of BASELINE.json ("other_configs"), and the rate of the
-runtime's own device-to-device copy on the box ("roofline.device_copy": context for the fractions of the nominal peak).
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either through torch.distributed.run (one rank per GPU,
-RANK / WORLD_SIZE in the environment) or plainly: without RANK the script starts the N ranks itself as a child process and
-relays rank 0's line.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step (--dump-outputs) and prints the line:
+the headline figures and the roofline of the timed kernels.  Everything else runs only with --full, outside the timed
+region: the decode with the encoder's index handed over ("decode_indexed_gbps"), the full-entropy variant, and at N=1 the
+reference's CPU path on a 1 GiB prefix ("cpu_baseline"), a byte-for-byte comparison of the WHOLE GPU frame with the
+reference's frames of its 1 GiB slices ("parity_bytes"), the host-pointer ABI end to end ("host_pointer"), the other
+configurations of BASELINE.json ("other_configs"), and the rate of the runtime's own device-to-device copy on the box
+("roofline.device_copy": context for the fractions of the nominal peak).
+
+--dump-outputs DIR writes what the last timed step produced, as float32 / float64 .npy files (about 25 MB in all, the
+same seeded positions every run, so that two builds can be compared output for output): compressed_size; frame_head
+(the first 64 KiB of the frame); frame_sample (2^21 frame bytes at sorted positions drawn with numpy's default_rng(1234)
+from [0, compressed_size)); frame_chunk_sums (per MiB of the frame: the sum of its bytes and the sum of byte x (offset in
+the MiB + 1)); decoded_sample (2^21 decoded elements as values, positions from default_rng(1235)); decoded_chunk_sums (the
+sum of the decoded values per 2^20 elements).  With N > 1 every rank writes its own, suffixed _rank<r>.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 either through
+torch.distributed.run (one rank per GPU, RANK / WORLD_SIZE in the environment) or plainly: without RANK the script starts
+the N ranks itself as a child process and relays rank 0's line.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import ctypes
@@ -47,11 +58,17 @@ def parse():
     p.add_argument("--config", choices=("int32", "int16", "double"), default="int32", help="BASELINE.json config: int32 = configs[1] (the headline), "
                    "int16 = one shard of configs[3], double = configs[2] at level 1")
     p.add_argument("--kind", default=None, help="another datagen kind for the chosen element size (experiments)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-full-entropy", action="store_true", help="skip the extra full-entropy (all COPY) measurement")
-    p.add_argument("--no-other-configs", action="store_true", help="skip the int16 / double / level 2 / level 3 entries")
+    p.add_argument("--full", action="store_true", help="also run everything beyond the headline: indexed decode, full entropy, CPU baseline, "
+                   "reference parity, host-pointer ABI, other configs, device copy rate, sharded exchange")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, the parity and host-pointer legs")
+    p.add_argument("--no-full-entropy", action="store_true", help="with --full: skip the extra full-entropy (all COPY) measurement")
+    p.add_argument("--no-other-configs", action="store_true", help="with --full: skip the int16 / double / level 2 / level 3 entries")
     p.add_argument("--cpu-sample-mib", type=int, default=1024)
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def cpu_share():
@@ -119,8 +136,9 @@ def cpu_baseline(sample, T, sample_desc, level=1, reps=5):
             "encode_gbps": round(nb / te / 1e9, 3), "decode_gbps": round(nb / td / 1e9, 3), "ratio": round(nb / r, 4)}
 
 
-def run_workload(st, torch, src, T, steps, warmup, dist, world, blocking=False):
-    """Returns wall seconds for `steps` round trips (max over ranks), per-direction seconds, kernel ms, csize."""
+def run_workload(st, torch, src, T, steps, warmup, dist, world, blocking=False, indexed_leg=True, on_last=None):
+    """Returns wall seconds for `steps` round trips (max over ranks), per-direction seconds, kernel ms, csize.
+    on_last(dst, csize, back) sees the frame and the decoded array of the last timed step, before anything else runs."""
     nbytes = src.numel()
     dst = torch.empty(st.bound(nbytes), dtype=torch.uint8, device=src.device)
     back = torch.empty_like(src)
@@ -176,17 +194,53 @@ def run_workload(st, torch, src, T, steps, warmup, dist, world, blocking=False):
         t = torch.tensor([wall], dtype=torch.float64, device=src.device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if on_last is not None:
+        on_last(dst, csize, back)
     ok = bool(torch.equal(back, src))
-    # extra leg, outside the timed region: the same decode with the encoder's index handed over (no walk)
-    back.zero_()
-    ev[0].record()
-    for _ in range(steps):
-        dec(csize, indexed=True)
-    ev[1].record()
-    ev[1].synchronize()
-    dec_indexed_s = ev[0].elapsed_time(ev[1]) / 1e3
-    ok = ok and bool(torch.equal(back, src))
+    dec_indexed_s = None
+    if indexed_leg:
+        # extra leg, outside the timed region: the same decode with the encoder's index handed over (no walk)
+        back.zero_()
+        ev[0].record()
+        for _ in range(steps):
+            dec(csize, indexed=True)
+        ev[1].record()
+        ev[1].synchronize()
+        dec_indexed_s = ev[0].elapsed_time(ev[1]) / 1e3
+        ok = ok and bool(torch.equal(back, src))
     return dict(wall=wall, enc_s=enc_s, dec_s=dec_s, dec_indexed_s=dec_indexed_s, kenc_ms=kenc / max(steps, 1), kdec_ms=kdec / max(steps, 1), csize=csize, ok=ok)
+
+
+DECODED_DTYPES = {1: "uint8", 2: "int16", 4: "int32", 8: "int64"}  # how a caller reads the decoded elements ("double": float64)
+
+
+def dump_outputs(out_dir, torch, dst, csize, back, T, float_data, suffix="", sample=1 << 21, chunk=1 << 20):
+    """The frame and the decoded array of the last timed step, as float32 / float64 .npy files (the module docstring lists
+    them).  Bounded: two samples of 2^21 values at seeded positions, the first 64 KiB of the frame, per-chunk sums."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+    frame = dst[:csize]
+    save("compressed_size", np.array([csize], dtype=np.float64))
+    save("frame_head", frame[: 64 << 10].cpu().numpy().astype(np.float32))
+    pos = np.sort(np.random.default_rng(1234).integers(0, csize, size=min(sample, csize), dtype=np.int64))
+    save("frame_sample", frame[torch.from_numpy(pos).to(frame.device)].cpu().numpy().astype(np.float32))
+    weight = torch.arange(1, chunk + 1, dtype=torch.int64, device=frame.device)
+    sums = []
+    for c0 in range(0, csize, chunk):
+        b = frame[c0:c0 + chunk].to(torch.int64)
+        sums.append(torch.stack([b.sum(), (b * weight[: b.numel()]).sum()]))
+    save("frame_chunk_sums", torch.stack(sums).cpu().numpy().astype(np.float64))
+    vals = back.view(torch.float64 if float_data and T == 8 else torch.float32 if float_data and T == 4 else getattr(torch, DECODED_DTYPES[T]))
+    n = vals.numel()
+    pos = np.sort(np.random.default_rng(1235).integers(0, n, size=min(sample, n), dtype=np.int64))
+    save("decoded_sample", vals[torch.from_numpy(pos).to(vals.device)].cpu().numpy().astype(np.float64))
+    acc = torch.float64 if float_data else torch.int64
+    save("decoded_chunk_sums", torch.stack([vals[c0:c0 + chunk].to(acc).sum() for c0 in range(0, n, chunk)]).cpu().numpy().astype(np.float64))
 
 
 CONFIGS = {
@@ -464,7 +518,11 @@ def main():
     else:
         src = generate_torch(kind, T, n, seed=42, device=dev, start=rank * n)
     torch.cuda.synchronize()
-    r = run_workload(st, torch, src, T, args.steps, args.warmup, dist, world)
+    on_last = None
+    if args.dump_outputs:
+        def on_last(dst, csize, back):
+            dump_outputs(args.dump_outputs, torch, dst, csize, back, T, kind == "sine", suffix=f"_rank{rank}" if world > 1 else "")
+    r = run_workload(st, torch, src, T, args.steps, args.warmup, dist, world, indexed_leg=args.full, on_last=on_last)
     assert r["ok"], "round trip mismatch"
     total_in = world * nbytes * args.steps
     value = total_in / r["wall"] / 1e9
@@ -479,7 +537,7 @@ def main():
         t_dec, _ = profiled_traffic(key, "decode_superblocks")
         roof = roofline("encode_superblocks", algo, r["kenc_ms"], traffic, source)
         roof["decode_superblocks"] = {k: v for k, v in roofline("decode_superblocks", algo, r["kdec_ms"], t_dec).items() if k in ("achieved", "frac", "kernel_ms", "traffic")}
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 roof["device_copy"] = device_copy_rate(torch, dev)
             except Exception as ex:  # (context only: never in the way of the line)
@@ -502,14 +560,16 @@ def main():
             "compression_ratio": round(ratio, 4),
             "encode_gbps": round(nbytes * args.steps / r["enc_s"] / 1e9, 3),
             "decode_gbps": round(nbytes * args.steps / r["dec_s"] / 1e9, 3),
-            "decode_input": "the frame alone: the superblock chain is walked on the device inside the timed region (csrc/walk.h); decode_indexed_gbps is the "
-                            "same decode with the encoder's index handed over (a decoder in the encoder's process), measured behind the timed region",
-            "decode_indexed_gbps": round(nbytes * args.steps / r["dec_indexed_s"] / 1e9, 3),
-            "value_with_indexed_decode": round(nbytes * args.steps / (r["enc_s"] + r["dec_indexed_s"]) / 1e9, 3),
-            "roofline": roof,
+            "decode_input": "the frame alone: the superblock chain is walked on the device inside the timed region (csrc/walk.h)",
         }
+        if args.full:
+            out["decode_input"] += ("; decode_indexed_gbps is the same decode with the encoder's index handed over (a decoder in the encoder's process), "
+                                    "measured behind the timed region")
+            out["decode_indexed_gbps"] = round(nbytes * args.steps / r["dec_indexed_s"] / 1e9, 3)
+            out["value_with_indexed_decode"] = round(nbytes * args.steps / (r["enc_s"] + r["dec_indexed_s"]) / 1e9, 3)
+        out["roofline"] = roof
     # the literal "random int32" variant: every superblock becomes COPY (reported next to the headline, with its own roofline)
-    if world == 1 and T == 4 and not args.kind and not args.no_full_entropy:
+    if args.full and world == 1 and T == 4 and not args.kind and not args.no_full_entropy:
         src2 = generate_torch("rand", T, n, seed=42, device=dev)
         k = max(1, min(3, args.steps))
         r2 = run_workload(st, torch, src2, T, k, 1, dist, world)
@@ -524,7 +584,7 @@ def main():
                                "encode_gbps": round(nbytes * k / r2["enc_s"] / 1e9, 3), "decode_gbps": round(nbytes * k / r2["dec_s"] / 1e9, 3),
                                "decode_indexed_gbps": round(nbytes * k / r2["dec_indexed_s"] / 1e9, 3), "roofline": roof2}
         del src2
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         mib = min(args.cpu_sample_mib, nbytes >> 20)
         sample_bytes = (mib << 20) + 4000 if (mib << 20) + 4000 <= nbytes else nbytes  # not a superblock multiple: the reference decoder rejects those
         sample = src[:sample_bytes].cpu().numpy()
@@ -534,12 +594,12 @@ def main():
         out["parity_frame_bytes"] = int(r["csize"])
         out["host_pointer"] = host_pointer_rate(T, sample)
         del sample
-    if world == 1 and args.config == "int32" and not args.kind and not args.no_other_configs:
+    if args.full and world == 1 and args.config == "int32" and not args.kind and not args.no_other_configs:
         del src
         torch.cuda.empty_cache()
         out["other_configs"] = {name: measure_other(name, torch, dist, dev, not args.no_cpu_baseline) for name in OTHER_CONFIGS}
         src = None
-    if world > 1:
+    if args.full and world > 1:
         # The one exchange of the sharded form, after the timed region and timed on its own: the compressed segments go to
         # rank 0 (RCCL over xGMI with the nccl backend), rank 0 cuts the assembled frame again and every rank decodes its
         # segment; each rank checks its slice against its input.

@@ -162,8 +162,8 @@ def test_fused_launch_that_gives_up_is_redone_without_the_fused_kernel(hooks_lib
 
 
 def test_bench_two_ranks_on_one_gpu(tmp_path):
-    """bench.py's N > 1 control flow (rank sharding, barrier, max over ranks, one JSON line from rank 0)
-    exercised with two processes on the single GPU of the test box (gloo for the two collectives)."""
+    """bench.py's N > 1 control flow (rank sharding, barrier, max over ranks, one JSON line from rank 0, and with --full the
+    sharded exchange) exercised with two processes on the single GPU of the test box (gloo for the two collectives)."""
     import json
     import os
     import subprocess
@@ -172,7 +172,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, STENOS_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gib", "0.25"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gib", "0.25", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-1500:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

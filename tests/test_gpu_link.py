@@ -1,5 +1,6 @@
 """Link-level checks of the drop-in boundary (tests/link): programs compiled against the C header and linked with
--lstenos, run on the GPU box.  The binaries are built by tests/link/Makefile (__graft_entry__.build()) into build/."""
+-lstenos, run on the GPU.  build() makes them: the C program with tests/link/Makefile into build/, the reference's own
+tests with oracle/Makefile into oracle/_ref/ (where the reference's sources are, and kept prebuilt where they are not)."""
 import os
 import subprocess
 
@@ -11,9 +12,10 @@ pytestmark = pytest.mark.gpu
 
 
 def _binary(name):
-    path = os.path.join(ROOT, "build", name)
+    where, recipe = ("build", "tests/link/Makefile") if name == "abi_link" else (os.path.join("oracle", "_ref"), "oracle/Makefile")
+    path = os.path.join(ROOT, where, name)
     if not os.path.exists(path):
-        pytest.skip(f"build/{name} was not built (tests/link/Makefile)")
+        pytest.skip(f"{where}/{name} was not built ({recipe})")
     return path
 
 
