@@ -96,7 +96,9 @@ STENOS_EXPORT int stenos_hip_fused_fallbacks(stenos_context* ctx);
  * stenos_hip_test_walk: serial != 0 makes frames that come without an index be walked by one lane (the serial walk that the
  * parallel one of walk.h is proven against, and falls back to); returns whether the last parallel walk on ctx fell back to
  * the serial one (1), did not (0), or there was none (-1).
- * stenos_hip_test_fused_timeouts: the next n fused launches are treated as if they had given up waiting. */
+ * stenos_hip_test_fused_timeouts: n > 0: the next n fused launches are treated as if they had given up waiting.  n = -1 - v,
+ * v in 0..2: which fused encoder the calls on ctx launch from now on -- v = 0 the library's own rule (the default), 1 the plain
+ * kernel, 2 the non-temporal one where the bytesoftype has it (4; the plain one elsewhere). */
 STENOS_EXPORT void stenos_hip_test_lanes(stenos_context* ctx, int share_current_device, int fail_lane);
 STENOS_EXPORT int stenos_hip_test_walk(stenos_context* ctx, int serial);
 STENOS_EXPORT void stenos_hip_test_fused_timeouts(stenos_context* ctx, int n);

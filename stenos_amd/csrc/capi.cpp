@@ -237,9 +237,9 @@ struct stenos_context_s {
 	DevBuf dslots, dtab;                             // levels >= 2, device destinations: zstd output slots of two batches and their offset / size tables
 	bool test_serial_walk = false;                   // (only the test build can set it) stenos_hip_test_walk: frames without an index are walked by one lane
 	DevBuf wide;                                     // bytesoftype above 64: scratch of the HBM-resident kernels (kernels_wide.hip)
-	DevBuf misc;                                     // [0,8) total, [8,12) decode status, [12,16) encode status, [16,20) first flagged, [20,24) unused, [24,32) scan carry, [64,320) override payload
+	DevBuf misc;                                     // [0,8) total, [8,12) decode status, [12,16) encode status, [16,20) first flagged, [20,24) fused copies, [24,32) scan carry, [64,320) override payload
 	HostBuf h_in, h_out, h_blocks, h_shuf, h_mid0, h_mid1, h_stage, h_tab; // host staging of the strategy layer
-	uint64_t* h_total = nullptr;                     // pinned copy of misc[0,16) for compress; decode status at +32
+	uint64_t* h_total = nullptr;                     // pinned copy of misc[0,24) for compress; decode status at +32
 	// last asynchronous job
 	hipStream_t job_stream = nullptr;
 	int job_kind = 0; // 0 none, 1 compress, 2 decompress
@@ -268,6 +268,9 @@ struct stenos_context_s {
 	bool no_fused = false;
 	int fused_fallbacks = 0;      // times that happened (stenos_hip_fused_fallbacks)
 	int inject_chain_timeout = 0; // (only the test build can set it, stenos_hip_test_fused_timeouts) the next n fused launches are treated as if they had given up
+	int test_fused_variant = 0;   // (only the test build can set it, stenos_hip_test_fused_timeouts(ctx, -1 - v)) v = 0: the rule of enqueue_compress, 1: plain, 2: nt
+	bool fused_copy_heavy = false; // the last fused call on this context stored more than half its superblocks as copies
+	uint64_t job_fused_nsb = 0;    // superblocks of the pending job's fused launch (0: none); its copy count comes back at misc + 20
 	int device = -1; // the device the buffers above live on (the one that was current when they were first needed)
 	// host-pointer calls with stenos_set_threads(ctx, n > 1): one child context per further device (or per stand-in lane),
 	// used from a host thread of its own (multi_device below)
@@ -434,6 +437,12 @@ bool wide_scratch(stenos_context_s* ctx, size_t T, uint64_t units, uint8_t** p, 
 }
 // levels >= 2 and bytesoftype 1 go through the strategy layer (block codec on the GPU + zstd on the host)
 inline bool needs_strategy(size_t T, int level) { return level >= 2 || (level == 1 && T == 1); }
+// staging of the fused encoder, whichever of its kernels a call launches
+inline size_t fused_stage_bytes_any(uint32_t T, uint32_t bps, uint64_t nsb)
+{
+	const size_t plain = stenos_k_fused_stage_bytes(T, bps, nsb, false), nt = stenos_k_fused_nt_supported(T) ? stenos_k_fused_stage_bytes(T, bps, nsb, true) : 0;
+	return plain > nt ? plain : nt;
+}
 
 // Enqueue the compression of `bytes` device bytes into a frame (or, with frame_header == false, into
 // the bare superblock stream used by the private API).  Nothing is waited for except, for a final
@@ -514,8 +523,16 @@ size_t enqueue_compress(stenos_context_s* ctx, const uint8_t* d_src, size_t T, s
 	// One arena serves both: the staging streams of the fused superblocks, then (the fused kernel is done by
 	// then) the 16-byte aligned slots of the remaining blocks, addressed by their absolute block number.
 	const uint64_t b_unfused = first_block(s_fused);
+	// Which fused kernel.  Bytesoftype 4 takes encode_superblocks_nt (non-temporal input and frame, fewer workgroups: the
+	// staged streams stay in the caches) unless the context's last fused call stored more than half its superblocks
+	// as copies: incompressible input reads its source twice (a measuring pass, then the copy or a second pass), and there the
+	// policy costs instead (full entropy +30 %).  Like the guess of a workgroup inside the kernel, history decides.
+	bool fused_nt = stenos_k_fused_nt_supported((uint32_t)T) && !ctx->fused_copy_heavy;
+	if (ctx->test_fused_variant)
+		fused_nt = ctx->test_fused_variant == 2 && stenos_k_fused_nt_supported((uint32_t)T);
 	if (level >= 1) {
-		const size_t stage_bytes = s_fused ? stenos_k_fused_stage_bytes((uint32_t)T, f.bps, s_fused) : 0;
+		// (the arena fits either kernel's staging buffers, so that a change of kernel between calls allocates nothing)
+		const size_t stage_bytes = s_fused ? fused_stage_bytes_any((uint32_t)T, f.bps, s_fused) : 0;
 		const size_t slot_bytes = (size_t)(nblocks_all - b_unfused + 1) * stride;
 		if (!ctx->slots.ensure(stage_bytes > slot_bytes ? stage_bytes : slot_bytes))
 			return STENOS_ERROR_ALLOC;
@@ -528,7 +545,8 @@ size_t enqueue_compress(stenos_context_s* ctx, const uint8_t* d_src, size_t T, s
 		if (stenos_k_launch_init(misc, header, ctx->chain.as<uint64_t>(), s_fused + 2, j.sb_off, s_fused + 8, stream) != hipSuccess)
 			return STENOS_ERROR_UNDEFINED;
 		ctx->mark(0, stream);
-		if (stenos_k_launch_encode_fused(j, s_fused, ctx->slots.as<uint8_t>(), desc, ctx->chain.as<uint32_t>(), d_carry, stream) != hipSuccess)
+		if (stenos_k_launch_encode_fused(j, s_fused, ctx->slots.as<uint8_t>(), desc, ctx->chain.as<uint32_t>(), d_carry, (uint32_t*)(misc + 20), fused_nt, stream) !=
+		    hipSuccess)
 			return STENOS_ERROR_UNDEFINED;
 		ctx->mark(1, stream);
 	}
@@ -600,9 +618,10 @@ size_t enqueue_compress(stenos_context_s* ctx, const uint8_t* d_src, size_t T, s
 	}
 	if (stenos_k_launch_pack(j, s_tight, f.nsb, stream) != hipSuccess)
 		return STENOS_ERROR_UNDEFINED;
-	// total (8 bytes) and the encode status (4 bytes at +12) travel together
-	if (hipMemcpyAsync(ctx->h_total, misc, 16, hipMemcpyDeviceToHost, stream) != hipSuccess)
+	// total (8 bytes), the encode status (4 bytes at +12) and the fused kernel's copy count (+20) travel together
+	if (hipMemcpyAsync(ctx->h_total, misc, 24, hipMemcpyDeviceToHost, stream) != hipSuccess)
 		return STENOS_ERROR_UNDEFINED;
+	ctx->job_fused_nsb = s_fused;
 	ctx->last_nsb = f.nsb;
 	return 0;
 }
@@ -2623,6 +2642,8 @@ void stenos_hip_test_fused_timeouts(stenos_context* ctx, int n)
 {
 	if (ctx && n > 0)
 		ctx->inject_chain_timeout = n;
+	if (ctx && n < 0 && n >= -3) // (the choice of fused kernel rides on this switch: the set of test switches is fixed, tests/test_abi_cpu.py)
+		ctx->test_fused_variant = -n - 1;
 }
 #endif
 int stenos_hip_device_count(void)
@@ -2643,7 +2664,7 @@ size_t stenos_hip_workspace_bytes(size_t bytesoftype, size_t bytes)
 	// the arena: staging buffers of the fused encoder (two per resident workgroup, whatever the input size) plus the slots of
 	// the last superblocks or, where that kernel does not apply, one padded slot per block; then 12 bytes of tables per block
 	// and 37 per superblock (default superblock size).  (A destination below stenos_bound() sends every block through slots.)
-	const size_t arena = stenos_k_fused_supported(T) ? stenos_k_fused_stage_bytes(T, (uint32_t)(sb / bs), nsb) + 2 * (sb / bs + 1) * stenos_k_slot_stride(T)
+	const size_t arena = stenos_k_fused_supported(T) ? fused_stage_bytes_any(T, (uint32_t)(sb / bs), nsb) + 2 * (sb / bs + 1) * stenos_k_slot_stride(T)
 							 : nblocks * (size_t)stenos_k_slot_stride(T);
 	size_t wide = 0; // bytesoftype above 64: the scratch of kernels_wide.hip (wide_scratch())
 	if (T > STENOS_K_LDS_MAX_T) {
@@ -2685,6 +2706,11 @@ size_t finish_job(stenos_context_s* ctx)
 	const int kind = ctx->job_kind;
 	ctx->job_kind = 0;
 	if (kind == 1) {
+		if (ctx->job_fused_nsb) { // history for the next call's choice of fused kernel (enqueue_compress)
+			const uint32_t copies = *(const uint32_t*)((const uint8_t*)ctx->h_total + 20);
+			ctx->fused_copy_heavy = 2ull * copies > ctx->job_fused_nsb;
+			ctx->job_fused_nsb = 0;
+		}
 		const uint64_t total = ctx->h_total[0];
 		uint32_t estatus = *(const uint32_t*)((const uint8_t*)ctx->h_total + 12);
 		if (ctx->inject_chain_timeout > 0 && ctx->job_src && !ctx->no_fused) {

@@ -80,6 +80,8 @@ constexpr uint64_t CHAIN_FAILED = ~0ull;
 // CU).  bytesoftype 8: its four waves need 30 KB of LDS, so five workgroups are all a CU holds anyway -- saying so gives the
 // encoder 96 vector registers instead of 64 (double sine: 8.5 -> 8.2 ms per 8 GiB).
 constexpr uint32_t fused_occupancy(uint32_t TT) { return TT == 8 ? 5u : 8u; }
+// encode_superblocks_nt: waves per SIMD, and workgroups per CU
+constexpr uint32_t FUSED_NT_OCCUPANCY = 7;
 constexpr bool FUSED_SPECULATE = true; // raw bytes of measured superblocks go straight to where a copy behind copies stands
 
 __device__ inline void chain_put(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -87,7 +89,7 @@ __device__ inline uint64_t chain_get(const uint64_t* p) { return __hip_atomic_lo
 
 // one wavefront: sizes -> offsets, in order, up to 256 superblocks per round (four per lane, all loads in flight
 // together: the encoders finish a superblock every 0.1 us, a round trip to the sizes takes a few us)
-__device__ void chain_scanner(const FrameJob& j, uint64_t nsb, const uint64_t* size, uint64_t* carry)
+__device__ __forceinline__ void chain_scanner(const FrameJob& j, uint64_t nsb, const uint64_t* size, uint64_t* carry)
 {
 	constexpr uint32_t PER = 4;
 	const uint32_t lane = threadIdx.x & 63u;
@@ -143,7 +145,7 @@ __device__ void chain_scanner(const FrameJob& j, uint64_t nsb, const uint64_t* s
 }
 
 // offset of superblock s once the scanner has published it (every lane polls the same word)
-__device__ uint64_t chain_wait(const FrameJob& j, uint64_t s)
+__device__ __forceinline__ uint64_t chain_wait(const FrameJob& j, uint64_t s)
 {
 	for (uint32_t spins = 0; spins <= CHAIN_SPIN_LIMIT; ++spins) {
 		const uint64_t v = chain_get(j.sb_off + s);
@@ -162,10 +164,17 @@ __device__ uint64_t chain_wait(const FrameJob& j, uint64_t s)
 // Workgroup 0: the scanner.  Every other workgroup: FUSED_WAVES wavefronts that take superblocks one after the other
 // until none is left -- encode (each wave a run of consecutive blocks into its staging stream), publish the size, then
 // store the previous superblock at its offset (pipeline.h, fused_store): by then the scanner has normally passed it.
-// A workgroup owns two staging buffers and alternates between them.
-template <uint32_t TT>
-__global__ __launch_bounds__(64 * FUSED_WAVES, fused_occupancy(TT)) void encode_superblocks(FrameJob j, uint64_t nsb, uint8_t* __restrict__ stage, uint32_t run_cap,
-									uint64_t* __restrict__ size, uint32_t* __restrict__ ticket, uint64_t* __restrict__ carry)
+// A workgroup owns two staging buffers and alternates between them.  *copies: += the superblocks it stored as copies (the
+// host's choice of kernel for the next call, capi.cpp).
+//
+// NT: the cache policy of encode_superblocks_nt.  The bytes a staged line waits behind before it is read back are what
+// every resident workgroup loads and stores in the meantime; with the input of the passes that encode for real and the
+// frame stores non-temporal, that is the staging writes alone, and the staged streams come back from the caches instead
+// of HBM.  Measuring passes (their input is read a second time when they measured wrong), the copy of a
+// superblock's input into the frame, the staged streams and the chain words keep ordinary accesses.
+template <uint32_t TT, bool NT>
+__device__ __forceinline__ void encode_superblocks_body(FrameJob j, uint64_t nsb, uint8_t* __restrict__ stage, uint32_t run_cap, uint64_t* __restrict__ size,
+							uint32_t* __restrict__ ticket, uint64_t* __restrict__ carry, uint32_t* __restrict__ copies)
 {
 	if (blockIdx.x == 0) {
 		if (threadIdx.x < 64)
@@ -184,6 +193,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, fused_occupancy(TT)) void encode_
 	uint32_t prev_run[FUSED_WAVES];
 	bool guess_copy = false; // the workgroup's last superblock ended up as a copy
 	bool group_hint = true;  // the wave's last blocks had the shape that groups of four blocks want (superblock_codec.h)
+	uint32_t ncopies = 0;    // superblocks this workgroup stored as copies
 	if (threadIdx.x == 0)
 		shared[2] = 0;
 	for (uint32_t it = 0;; ++it) {
@@ -215,7 +225,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, fused_occupancy(TT)) void encode_
 				// those bytes writes them later -- later superblocks learn their offsets only after this one has published its
 				// size, which it does after its stores -- write-through: the XCDs' L2s are not coherent -- have completed.
 				uint8_t* const spec_to = measure && FUSED_SPECULATE ? j.dst + j.header_bytes + s * (uint64_t)(j.sb_bytes + 4) + 4 + (uint64_t)b0 * (256 * T) : nullptr;
-				const uint32_t n = encode_run(g_lds + w * L.total, L, T, from, b1 - b0, measure ? nullptr : to, true, NoPassHook(), spec_to, &group_hint);
+				const uint32_t n = NT && !measure ? encode_run<NoPassHook, NtSource>(g_lds + w * L.total, L, T, from, b1 - b0, to, true, NoPassHook(), nullptr, &group_hint)
+								  : encode_run(g_lds + w * L.total, L, T, from, b1 - b0, measure ? nullptr : to, true, NoPassHook(), spec_to, &group_hint);
 				if (spec_to)
 					gst_through_wait(); // (write-through stores: in memory before the size is published)
 				if ((threadIdx.x & 63u) == 0)
@@ -230,6 +241,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, fused_occupancy(TT)) void encode_
 					continue;
 				}
 				guess_copy = code == 6;
+				ncopies += guess_copy ? 1u : 0u;
 				spec_now = measure && FUSED_SPECULATE; // (its raw bytes stand at the speculated place; code is 6 here)
 				if (threadIdx.x == 0)
 					chain_put(size + s, bytes);
@@ -243,16 +255,37 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, fused_occupancy(TT)) void encode_
 			if (off == CHAIN_FAILED)
 				shared[2] = 1;
 			else
-				fused_store(j, prev, w, off, prev_run, stage_w + (uint64_t)(parity ^ 1u) * FUSED_WAVES * run_cap,
-					    prev_spec && off == j.header_bytes + prev * (uint64_t)(j.sb_bytes + 4));
+				fused_store<NT>(j, prev, w, off, prev_run, stage_w + (uint64_t)(parity ^ 1u) * FUSED_WAVES * run_cap,
+						prev_spec && off == j.header_bytes + prev * (uint64_t)(j.sb_bytes + 4));
 		}
-		if (!work)
+		if (!work) {
+			if (threadIdx.x == 0 && ncopies)
+				atomicAdd(copies, ncopies);
 			return;
+		}
 		prev = s;
 		prev_spec = spec_now;
 		for (uint32_t k = 0; k < FUSED_WAVES; ++k)
 			prev_run[k] = run_size[k];
 	}
+}
+
+template <uint32_t TT>
+__global__ __launch_bounds__(64 * FUSED_WAVES, fused_occupancy(TT)) void encode_superblocks(FrameJob j, uint64_t nsb, uint8_t* __restrict__ stage, uint32_t run_cap,
+									uint64_t* __restrict__ size, uint32_t* __restrict__ ticket, uint64_t* __restrict__ carry,
+									uint32_t* __restrict__ copies)
+{
+	encode_superblocks_body<TT, false>(j, nsb, stage, run_cap, size, ticket, carry, copies);
+}
+// The same with non-temporal input and frame (bytesoftype 4 only, capi.cpp), compiled for FUSED_NT_OCCUPANCY waves per SIMD and
+// launched with the LDS that leaves room for no more workgroups per CU than that: the fewer workgroups stage at a time, the
+// shorter the distance between a staged line's write and its read.
+template <uint32_t TT>
+__global__ __launch_bounds__(64 * FUSED_WAVES, FUSED_NT_OCCUPANCY) void encode_superblocks_nt(FrameJob j, uint64_t nsb, uint8_t* __restrict__ stage, uint32_t run_cap,
+									uint64_t* __restrict__ size, uint32_t* __restrict__ ticket, uint64_t* __restrict__ carry,
+									uint32_t* __restrict__ copies)
+{
+	encode_superblocks_body<TT, true>(j, nsb, stage, run_cap, size, ticket, carry, copies);
 }
 
 // One wavefront per superblock.
@@ -365,42 +398,65 @@ hipError_t stenos_k_launch_init(uint8_t* misc, uint64_t first_off, uint64_t* z1,
 	return hipGetLastError();
 }
 
-template <uint32_t TT>
-static hipError_t launch_fused_t(const FrameJob& j, uint64_t nsb, uint8_t* stage, uint64_t* desc, uint32_t* ticket, uint64_t* carry, hipStream_t stream)
+// LDS of a fused workgroup: the waves' scratch, the shared words.  The nt kernel asks for enough more that no more than
+// FUSED_NT_OCCUPANCY workgroups fit into the 160 KiB of a CU, whatever registers the compiler gave it: halfway between
+// the shares of N + 1 and N workgroups, so that the allocation granule cannot tip it either way.
+static size_t fused_lds_bytes(uint32_t T, bool nt)
 {
-	const size_t lds = FUSED_WAVES * stenos_k_encode_lds_bytes(j.T) + 32 + 8 * FUSED_WAVES;
-	hipError_t e = hipFuncSetAttribute((const void*)encode_superblocks<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	const size_t need = FUSED_WAVES * stenos_k_encode_lds_bytes(T) + 32 + 8 * FUSED_WAVES;
+	const size_t cu = 160u * 1024u, cap = (cu / (FUSED_NT_OCCUPANCY + 1) + cu / FUSED_NT_OCCUPANCY) / 2 & ~(size_t)255;
+	return nt && need < cap ? cap : need;
+}
+
+template <uint32_t TT, bool NT>
+static hipError_t launch_fused_t(const FrameJob& j, uint64_t nsb, uint8_t* stage, uint64_t* desc, uint32_t* ticket, uint64_t* carry, uint32_t* copies, hipStream_t stream)
+{
+	const size_t lds = fused_lds_bytes(j.T, NT);
+	const auto kernel = [] {
+		if constexpr (NT)
+			return encode_superblocks_nt<TT>;
+		else
+			return encode_superblocks<TT>;
+	}();
+	hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 	if (e != hipSuccess)
 		return e;
-	const uint32_t grid = stenos_k_fused_groups(nsb, j.T) + 1; // + the scanner
-	hipLaunchKernelGGL((encode_superblocks<TT>), dim3(grid), dim3(64 * FUSED_WAVES), lds, stream, j, nsb, stage, fused_run_capacity(j.bps, j.T), desc, ticket, carry);
+	const uint32_t grid = stenos_k_fused_groups(nsb, j.T, NT) + 1; // + the scanner
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * FUSED_WAVES), lds, stream, j, nsb, stage, fused_run_capacity(j.bps, j.T), desc, ticket, carry, copies);
 	return hipGetLastError();
 }
 
 // Superblocks [0, nsb) of the job, all of them bps full blocks with room for any encoding.  desc: nsb zeroed words,
-// ticket: one zeroed word, j.sb_off[0, nsb] zeroed, stage: stenos_k_fused_stage_bytes(); *carry receives the frame
-// offset behind them.
-hipError_t stenos_k_launch_encode_fused(const FrameJob& j, uint64_t nsb, uint8_t* stage, uint64_t* desc, uint32_t* ticket, uint64_t* carry, hipStream_t stream)
+// ticket: one zeroed word, j.sb_off[0, nsb] zeroed, stage: stenos_k_fused_stage_bytes(), copies: one zeroed word that
+// receives the number of superblocks stored as copies; *carry receives the frame offset behind them.  nt: the kernel with
+// the non-temporal policy (only where stenos_k_fused_nt_supported()).
+hipError_t stenos_k_launch_encode_fused(const FrameJob& j, uint64_t nsb, uint8_t* stage, uint64_t* desc, uint32_t* ticket, uint64_t* carry, uint32_t* copies, bool nt,
+					hipStream_t stream)
 {
 	if (nsb == 0)
 		return hipSuccess;
 	switch (j.T) {
-		case 2: return launch_fused_t<2>(j, nsb, stage, desc, ticket, carry, stream);
-		case 4: return launch_fused_t<4>(j, nsb, stage, desc, ticket, carry, stream);
-		case 8: return launch_fused_t<8>(j, nsb, stage, desc, ticket, carry, stream);
-		default: return launch_fused_t<0>(j, nsb, stage, desc, ticket, carry, stream);
+		case 2: return launch_fused_t<2, false>(j, nsb, stage, desc, ticket, carry, copies, stream);
+		case 4: return nt ? launch_fused_t<4, true>(j, nsb, stage, desc, ticket, carry, copies, stream) : launch_fused_t<4, false>(j, nsb, stage, desc, ticket, carry, copies, stream);
+		case 8: return launch_fused_t<8, false>(j, nsb, stage, desc, ticket, carry, copies, stream);
+		default: return launch_fused_t<0, false>(j, nsb, stage, desc, ticket, carry, copies, stream);
 	}
 }
 // the workgroup's scratch must fit the 160 KiB of a CU (bytesoftype up to about 40)
-bool stenos_k_fused_supported(uint32_t T) { return T <= STENOS_K_LDS_MAX_T && FUSED_WAVES * stenos_k_encode_lds_bytes(T) + 32 + 8 * FUSED_WAVES <= 160u * 1024u; }
+bool stenos_k_fused_supported(uint32_t T) { return T <= STENOS_K_LDS_MAX_T && fused_lds_bytes(T, false) <= 160u * 1024u; }
+bool stenos_k_fused_nt_supported(uint32_t T) { return T == 4; }
 // encoder workgroups of the fused kernel: as many as stay resident (they take superblocks until none is left)
-uint32_t stenos_k_fused_groups(uint64_t nsb, uint32_t T)
+uint32_t stenos_k_fused_groups(uint64_t nsb, uint32_t T, bool nt)
 {
-	const uint64_t resident = (uint64_t)stenos_k_cu_count() * (fused_occupancy(T) * 4 / FUSED_WAVES); // waves per SIMD x four SIMDs
+	const uint32_t occupancy = nt ? FUSED_NT_OCCUPANCY : fused_occupancy(T);
+	const uint64_t resident = (uint64_t)stenos_k_cu_count() * (occupancy * 4 / FUSED_WAVES); // waves per SIMD x four SIMDs
 	return (uint32_t)(nsb < resident ? nsb : resident);
 }
 // two staging buffers per workgroup
-size_t stenos_k_fused_stage_bytes(uint32_t T, uint32_t bps, uint64_t nsb) { return (size_t)stenos_k_fused_groups(nsb, T) * 2 * FUSED_WAVES * fused_run_capacity(bps, T) + 64; }
+size_t stenos_k_fused_stage_bytes(uint32_t T, uint32_t bps, uint64_t nsb, bool nt)
+{
+	return (size_t)stenos_k_fused_groups(nsb, T, nt) * 2 * FUSED_WAVES * fused_run_capacity(bps, T) + 64;
+}
 
 // blocks [b_begin, b_end) of the job (the tail block has index nfull)
 hipError_t stenos_k_launch_encode(const FrameJob& j, uint64_t b_begin, uint64_t b_end, hipStream_t stream)

@@ -272,7 +272,9 @@ WV_HD uint32_t fused_superblock_size(const FrameJob& j, const uint32_t* run_size
 }
 
 // wave w's share of writing superblock s at frame offset off.  payload_in_place: a copy whose raw bytes stand there already
-// (kernels.hip, speculative copy): only the headers are left to write.
+// (kernels.hip, speculative copy): only the headers are left to write.  NT_FRAME: the payload goes to the frame with
+// non-temporal stores (kernels.hip, encode_superblocks_nt); the staged stream and the input of a copy are read plainly either way.
+template <bool NT_FRAME = false>
 WV_FN void fused_store(const FrameJob& j, uint64_t s, uint32_t w, uint64_t off, const uint32_t* run_size, const uint8_t* stage_w, bool payload_in_place = false)
 {
 	const U32 lane = lane_id();
@@ -294,13 +296,13 @@ WV_FN void fused_store(const FrameJob& j, uint64_t s, uint32_t w, uint64_t off, 
 		uint32_t before = 0;
 		for (uint32_t k = 0; k < w; ++k)
 			before += run_size[k];
-		copy_g2g_wide(base + 4 + before, stage_w, run_size[w]);
+		copy_g2g_wide<COPY_ROUNDS, NT_FRAME>(base + 4 + before, stage_w, run_size[w]);
 	}
 	else if (!payload_in_place) {
 		uint32_t b0, b1;
 		fused_run_range(j.bps, w, &b0, &b1);
 		const uint32_t bs = 256 * j.T;
-		copy_g2g_wide(base + 4 + (uint64_t)b0 * bs, j.src + (s * j.bps + b0) * (uint64_t)bs, (b1 - b0) * bs);
+		copy_g2g_wide<COPY_ROUNDS, NT_FRAME>(base + 4 + (uint64_t)b0 * bs, j.src + (s * j.bps + b0) * (uint64_t)bs, (b1 - b0) * bs);
 	}
 }
 

@@ -239,8 +239,46 @@ struct RawProofHint {
 struct NoPassHook {
 	WV_MFN void operator()() const {}
 };
+// Where a pass takes its input blocks from, and with which cache policy (kernels.hip: encode_superblocks, encode_superblocks_nt).
+// PlainSource: ordinary loads.  NtSource: non-temporal loads (wavevec.h), for input that is read once.
+struct PlainSource {
+	WV_FN RawBlock raw_block(const uint8_t* g, uint32_t T) { return load_raw_block(g, T); }
+	WV_FN RawBlock8 raw_block8(const uint8_t* g) { return load_raw_block8(g); }
+	WV_FN void block(Lds lds, uint32_t ldsoff, const uint8_t* g, uint32_t n) { load_block(lds, ldsoff, g, n); }
+};
+#ifndef WV_HOST_EMULATION
+struct NtSource {
+	WV_FN RawBlock raw_block(const uint8_t* g, uint32_t T)
+	{
+		RawBlock r;
+		if (T == 2) {
+			gld64_nt(g, lane_id() * 8u, r.e.x, r.e.y);
+			r.e.z = r.e.w = U32(0u);
+		}
+		else
+			r.e = gld128_nt(g, lane_id() * 16u);
+		return r;
+	}
+	WV_FN RawBlock8 raw_block8(const uint8_t* g)
+	{
+		RawBlock8 r;
+		r.a = gld128_nt(g, lane_id() * 32u);
+		r.b = gld128_nt(g, lane_id() * 32u + 16u);
+		return r;
+	}
+	// n: a multiple of 16 (whole blocks); lanes beyond the end repeat the last group (the same bytes to the same place)
+	WV_FN void block(Lds lds, uint32_t ldsoff, const uint8_t* g, uint32_t n)
+	{
+		const U32 lane = lane_id();
+		for (uint32_t o = 0; o < n; o += 1024) {
+			const U32 off = umin(U32(o) + lane * 16u, U32(n - 16u));
+			lds_st128(lds, U32(ldsoff) + off, gld128_nt(g, off), pred_all(true));
+		}
+	}
+};
+#endif
 // hook(): called after every pass of the slot loop (a wave may have other work waiting: kernels.hip, early store)
-template <class Sink, class Hook = NoPassHook>
+template <class Sink, class Hook = NoPassHook, class Src = PlainSource>
 WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, const uint8_t* src, uint32_t nblocks, bool slots, Hook hook = Hook())
 {
 	if (slots && (T == 2 || T == 4 || T == 8))
@@ -261,7 +299,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 		auto group4 = [&]() __attribute__((always_inline)) -> bool {
 			const uint8_t* a = src + (uint64_t)i * bs;
 			WV_MARK("g4_load");
-			const RawBlock e0 = load_raw_block(a, T), e1 = load_raw_block(a + bs, T), e2 = load_raw_block(a + 2 * bs, T), e3 = load_raw_block(a + 3 * bs, T);
+			const RawBlock e0 = Src::raw_block(a, T), e1 = Src::raw_block(a + bs, T), e2 = Src::raw_block(a + 2 * bs, T), e3 = Src::raw_block(a + 3 * bs, T);
 			const Layout M = sink.at(L);
 			WV_MARK("g4_front");
 			const SameScan s0 = scan_same_fast(e0, T);
@@ -360,7 +398,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 #pragma unroll
 			for (uint32_t q = 0; q < NBMAX; ++q)
 				if (q < NB && q < avail)
-					e[q] = load_raw_block(a + (uint64_t)q * bs, T);
+					e[q] = Src::raw_block(a + (uint64_t)q * bs, T);
 			const Layout M = sink.at(L);
 			WV_MARK("ga_front");
 			// the blocks that fit: their masks packed T bits a block, their first elements in the table
@@ -445,7 +483,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 						if (f * 3 > bs && lz_precheck_passes(T, keys[q], f)) {
 							// (the count over 40 values turns most blocks away; one it does not is looked at again, as in the pass below: the
 							// test that turns noise away, then the count over all 80 values)
-							const RawBlock again = load_raw_block(a + (uint64_t)q * bs, T);
+							const RawBlock again = Src::raw_block(a + (uint64_t)q * bs, T);
 							cand = !lz_repeats_reject(lds, M, again.e, f) && lz_precheck_passes(T, lz_distinct_keys_fast<4>(lds, M, again.e), f);
 						}
 					}
@@ -496,14 +534,14 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 			{
 				// both blocks are requested at once, straight into registers; when the second one is not paired after all,
 				// its load has at least brought it closer for the next round
-				const RawBlock ea = load_raw_block(a, T);
+				const RawBlock ea = Src::raw_block(a, T);
 				RawBlock eb, ec, ed;
 				if (has_b)
-					eb = load_raw_block(b, T);
+					eb = Src::raw_block(b, T);
 				const bool early = has_b && i < wide_ahead;
 				if (early) {
-					ec = load_raw_block(b + bs, T);
-					ed = load_raw_block(b + 2 * bs, T);
+					ec = Src::raw_block(b + bs, T);
+					ed = Src::raw_block(b + 2 * bs, T);
 				}
 				wide_ahead = 0;
 				WV_MARK("block_begin");
@@ -547,9 +585,9 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 				if (has_b && B.nslots <= 2) { WV_NESTED(); if (nblk == 2 && B.nact0 <= 1 && B.nslots - B.nact0 <= 1 && i + 2 < nblocks) {
 					const bool has_d = i + 3 < nblocks;
 					if (!early) {
-						ec = load_raw_block(b + bs, T);
+						ec = Src::raw_block(b + bs, T);
 						if (has_d)
-							ed = load_raw_block(b + 2 * bs, T);
+							ed = Src::raw_block(b + 2 * bs, T);
 					}
 					const SameScan sc = scan_same_fast(ec, T);
 					if (sc.nact <= 1) {
@@ -633,12 +671,12 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 					// repeat), then the key count over all 80 values.
 					// (constant indices: a loop over the blocks would send the batch's scalars through memory)
 					if (B.full[0] * 3 > bs && lz_precheck_passes(T, keys0, B.full[0])) {
-						const RawBlock e = load_raw_block(a, T);
+						const RawBlock e = Src::raw_block(a, T);
 						if (!lz_repeats_reject(lds, M, e.e, B.full[0]) && lz_precheck_passes(T, lz_distinct_keys_fast<4>(lds, M, e.e), B.full[0]))
 							lzq |= 1u, lds_st32(lds, U32(M.plinfo), U32(B.full[0]), lane_id() == U32(0u));
 					}
 					if (nblk > 1 && B.full[1] * 3 > bs && lz_precheck_passes(T, keys1, B.full[1])) {
-						const RawBlock e = load_raw_block(b, T);
+						const RawBlock e = Src::raw_block(b, T);
 						if (!lz_repeats_reject(lds, M, e.e, B.full[1]) && lz_precheck_passes(T, lz_distinct_keys_fast<4>(lds, M, e.e), B.full[1]))
 							lzq |= 2u, lds_st32(lds, U32(M.plinfo + 4), U32(B.full[1]), lane_id() == U32(0u));
 					}
@@ -669,7 +707,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 			wave_sync();
 			const uint32_t lzfull0 = readlane(lds_ld32(lds, U32(L.plinfo)), 0), lzfull1 = readlane(lds_ld32(lds, U32(L.plinfo + 4)), 0);
 			for (uint32_t q = 0; q < nblk; ++q) {
-				load_block(lds, L.in, q ? b : a, bs);
+				Src::block(lds, L.in, q ? b : a, bs);
 				wave_sync();
 				const Layout M = sink.at(L);
 				const uint32_t n = ((lzq >> q) & 1u) ? lz_try(lds, M, T, q ? lzfull1 : lzfull0, sink.base()) : 0u;
@@ -712,7 +750,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 		for (uint32_t i = 0; i < nblocks; ++i) {
 			const uint8_t* a = src + (uint64_t)i * bs;
 			WV_MARK("load_block");
-			const RawBlock8 eb = load_raw_block8(a);
+			const RawBlock8 eb = Src::raw_block8(a);
 			const Layout M = sink.at(L);
 			WV_MARK("block_begin");
 			const SameScan8 sc = scan_same8(eb);
@@ -753,7 +791,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 			}
 			const uint32_t full = pt0 + pt1 + (8 - sc.nact);
 			if (full * 3 > bs && lz_precheck_passes(8, keys, full) && !lz_repeats_reject8(lds, M, eb, full)) { // a mini-LZ attempt: the general block encoder
-				load_block(lds, L.in, a, bs);
+				Src::block(lds, L.in, a, bs);
 				wave_sync();
 				const uint32_t n = lz_try(lds, M, 8, full, sink.base()); // (its size without the mini-LZ is known: nothing else is needed)
 				if (n) {
@@ -783,7 +821,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 		return;
 	}
 	for (uint32_t i = 0; i < nblocks; ++i) {
-		load_block(lds, L.in, src + (uint64_t)i * (256 * T), 256 * T);
+		Src::block(lds, L.in, src + (uint64_t)i * (256 * T), 256 * T);
 		wave_sync();
 		if (sink.raw_to) // (measured only, probably a copy: the raw bytes go where the copy would put them)
 			for (uint32_t o = 0; o < 256 * T; o += 1024) {
@@ -799,7 +837,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 // ... into a staging stream at stage (16-byte aligned, room for nblocks * max_block_bytes(T) + 16); returns the bytes
 // (stage == nullptr: nothing is written, only the bytes are counted)
 // raw_to (only without a stage): the blocks' raw bytes are stored there on the way (StreamSink::raw_to)
-template <class Hook = NoPassHook>
+template <class Hook = NoPassHook, class Src = PlainSource>
 WV_FN uint32_t encode_run(Lds lds, const Layout& L, uint32_t T, const uint8_t* src, uint32_t nblocks, uint8_t* stage, bool slots = true, Hook hook = Hook(),
 			  uint8_t* raw_to = nullptr, bool* group_hint = nullptr)
 {
@@ -811,7 +849,7 @@ WV_FN uint32_t encode_run(Lds lds, const Layout& L, uint32_t T, const uint8_t* s
 	sink.raw_to = stage ? nullptr : raw_to;
 	if (sink.writes)
 		stream_begin(lds, L.out);
-	encode_blocks_to(sink, lds, L, T, src, nblocks, slots, hook);
+	encode_blocks_to<StreamSink, Hook, Src>(sink, lds, L, T, src, nblocks, slots, hook);
 	if (sink.writes)
 		stream_flush(sink.rs, lds, L.out);
 	return sink.rs.pos;
@@ -821,9 +859,21 @@ WV_FN uint32_t encode_run(Lds lds, const Layout& L, uint32_t T, const uint8_t* s
 // serve unaligned global accesses in hardware, so no lane reads a byte outside [src, src + n) and nothing has to be
 // shifted together from two aligned groups.  COPY_ROUNDS rounds of 64 groups at a time: all their loads are requested
 // before the first store, so the rounds cost one memory round trip.
+// NT_STORE: the 16-byte groups are written non-temporally (wavevec.h; the frame of kernels.hip's encode_superblocks_nt).
 constexpr uint32_t COPY_ROUNDS = 4;
+template <bool NT_STORE>
+WV_FN void gst128_copy_out(uint8_t* g, U32 off, const U128& v, Pred p)
+{
+#ifndef WV_HOST_EMULATION
+	if (NT_STORE) {
+		gst128_nt(g, off, v, p);
+		return;
+	}
+#endif
+	gst128_streamed(g, off, v, p);
+}
 #ifdef WV_PREDICATE_BRANCHES
-template <uint32_t ROUNDS = COPY_ROUNDS>
+template <uint32_t ROUNDS = COPY_ROUNDS, bool NT_STORE = false>
 WV_FN void copy_g2g_wide(uint8_t* dst, const uint8_t* src, uint32_t n)
 {
 	const U32 lane = lane_id();
@@ -844,7 +894,7 @@ WV_FN void copy_g2g_wide(uint8_t* dst, const uint8_t* src, uint32_t n)
 		}
 		for (uint32_t q = 0; q < ROUNDS; ++q) {
 			const U32 k = U32(o + 64 * q) + lane;
-			gst128(d, k * 16u, a[q], k < U32(groups));
+			gst128_copy_out<NT_STORE>(d, k * 16u, a[q], k < U32(groups));
 		}
 	}
 	const uint32_t done = h + groups * 16;
@@ -855,7 +905,7 @@ WV_FN void copy_g2g_wide(uint8_t* dst, const uint8_t* src, uint32_t n)
 }
 
 #else
-template <uint32_t ROUNDS = COPY_ROUNDS>
+template <uint32_t ROUNDS = COPY_ROUNDS, bool NT_STORE = false>
 WV_FN void copy_g2g_wide(uint8_t* dst, const uint8_t* src, uint32_t n)
 {
 	const U32 lane = lane_id();
@@ -876,7 +926,7 @@ WV_FN void copy_g2g_wide(uint8_t* dst, const uint8_t* src, uint32_t n)
 		for (uint32_t q = 0; q < ROUNDS; ++q)
 			if (o + 64 * q < groups) {
 				const U32 k = U32(o + 64 * q) + lane;
-				gst128_streamed(d, k * 16u, a[q], k < U32(groups));
+				gst128_copy_out<NT_STORE>(d, k * 16u, a[q], k < U32(groups));
 			}
 	}
 	const uint32_t done = h + groups * 16;

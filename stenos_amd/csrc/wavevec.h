@@ -662,6 +662,33 @@ WV_FN void gst64_through(uint8_t* g, U32 off, U32 lo, U32 hi)
 	asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2 sc0 sc1\n\ts_nop 1" : : "v"(off), "v"(d), "s"(wave_base(g)) : "memory");
 }
 WV_FN void gst_through_wait() { asm volatile("s_waitcnt vmcnt(0)" : : : "memory"); }
+// Non-temporal accesses (the nt bit): bytes that this kernel touches once -- the input of a pass that encodes for real, the frame
+// it writes -- and that should not displace the ones it comes back to (the staged streams) from the caches on their way
+// (kernels.hip, encode_superblocks_nt).  Loads by all lanes from any byte address; plain C++, so the compiler counts and
+// waits for them as for its own.
+// (global address space said explicitly: through a generic pointer they become flat accesses, which may alias the stack, and
+// the compiler then keeps the encoder's arrays in scratch memory)
+typedef uint32_t wv_u4_a1 __attribute__((ext_vector_type(4), aligned(1)));
+typedef uint32_t wv_u2_a1 __attribute__((ext_vector_type(2), aligned(1)));
+#define WV_GLOBAL __attribute__((address_space(1)))
+WV_FN U128 gld128_nt(const uint8_t* g, U32 off)
+{
+	const wv_u4_a1 v = __builtin_nontemporal_load((const WV_GLOBAL wv_u4_a1*)(g + off));
+	U128 r = { v.x, v.y, v.z, v.w };
+	return r;
+}
+WV_FN void gld64_nt(const uint8_t* g, U32 off, U32& lo, U32& hi)
+{
+	const wv_u2_a1 v = __builtin_nontemporal_load((const WV_GLOBAL wv_u2_a1*)(g + off));
+	lo = v.x;
+	hi = v.y;
+}
+WV_FN void gst128_nt(uint8_t* g, U32 off, const U128& v, Pred p)
+{
+	const wv_u4 d = { v.x, v.y, v.z, v.w };
+	if (p)
+		__builtin_nontemporal_store(d, (WV_GLOBAL wv_u4*)(g + off));
+}
 // wave-uniform scalar accesses to global memory (stores by one lane)
 WV_FN uint32_t gload_uniform(const uint32_t* p) { return *(const volatile uint32_t*)p; }
 WV_FN uint32_t gload_uniform8(const uint8_t* p) { return *(const volatile uint8_t*)p; }
