@@ -55,6 +55,32 @@ STENOS_EXPORT const uint64_t* stenos_hip_frame_index(stenos_context* ctx, const 
 STENOS_EXPORT size_t stenos_hip_decompress(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, void* d_dst, size_t dst_size, const uint64_t* d_index, void* stream);
 STENOS_EXPORT size_t stenos_hip_decompress_async(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, void* d_dst, size_t dst_size, const uint64_t* d_index, void* stream);
 
+/* Batches: n independent arrays -> n independent frames, and back, in one pass of kernels (the fixed cost of a call is paid
+ * once per batch instead of once per array).  d_srcs, d_dsts: host arrays of n DEVICE pointers; bytes / src_sizes, dst_sizes:
+ * host arrays of n sizes.  results[i] receives item i's frame size (decompressed size) or an error code (test with
+ * stenos_has_error): exactly what stenos_hip_compress (stenos_hip_decompress without an index) returns for that item alone,
+ * and compressed frames are byte-identical to that call's.  Nothing is written at or past dst_sizes[i]; items' destinations
+ * must not overlap.  Waits for completion.  Returns 0 when the batch ran (per-item outcomes in results[]; n == 0 returns 0),
+ * or an error code for the call as a whole, with results[] and the destinations untouched:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        compression at level >= 2, bytesoftype 1 at level 1 (both take the host strategy
+ *                                         layer), a time limit set on ctx; either direction with bytesoftype outside 1..64,
+ *                                         or while an _async job on ctx is unfinished (that job is left alone).
+ * Every item uses ctx's level and block-size settings and the one bytesoftype of the call.  Decompression accepts any frame
+ * stenos_hip_decompress accepts; superblocks with zstd-based codes (levels >= 2, the last superblock under 128 bytes of a level-1
+ * frame) are finished on the host item by item, which is slow.  Measured on MI355X (int32, level 1, profiles/batch_rate.txt):
+ * 4096 items of 64 KiB compress at 436 GB/s and decompress at 821 GB/s, 390x and 1100x a loop of single calls; the batch has
+ * no fused encoder, so for items between 64 MiB (batch 759 GB/s, loop 447) and 256 MiB (batch 770, single call 1 716) and above,
+ * compression becomes faster through stenos_hip_compress; decompression in a batch is never slower.  After a batch (either direction), stenos_hip_last_index returns NULL
+ * with *nsb = 0. */
+STENOS_EXPORT size_t stenos_hip_compress_batch(stenos_context* ctx, size_t n, size_t bytesoftype, const void* const* d_srcs, const size_t* bytes,
+					       void* const* d_dsts, const size_t* dst_sizes, size_t* results, void* stream);
+STENOS_EXPORT size_t stenos_hip_decompress_batch(stenos_context* ctx, size_t n, size_t bytesoftype, const void* const* d_srcs, const size_t* src_sizes,
+						 void* const* d_dsts, const size_t* dst_sizes, size_t* results, void* stream);
+/* Device workspace a compress batch of these n sizes needs (capacity planning, like stenos_hip_workspace_bytes); 0 for a
+ * bytesoftype outside 1..64. */
+STENOS_EXPORT size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t n, const size_t* bytes);
+
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),
  * byte delta in four quarter streams above 2048 bytes and its inverse.  src and dst must not overlap.

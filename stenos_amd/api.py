@@ -90,6 +90,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_unshuffle": (sz, [vp, sz, sz, vp, vp]),
         "stenos_hip_delta": (sz, [vp, vp, sz, vp]),
         "stenos_hip_delta_inv": (sz, [vp, vp, sz, vp]),
+        "stenos_hip_compress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
+        "stenos_hip_decompress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
+        "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
     }
@@ -190,3 +193,24 @@ class Stenos:
     def decompress(self, frame, bytesoftype: int, csize: int, dst, index_ptr: int | None = None, wait: bool = True) -> int:
         fn = self.lib.stenos_hip_decompress if wait else self.lib.stenos_hip_decompress_async
         return self._check(fn(self.ctx, frame.data_ptr(), bytesoftype, csize, dst.data_ptr(), dst.numel(), index_ptr, self._stream_ptr()))
+
+    def _batch(self, fn, srcs, bytesoftype: int, sizes, dsts) -> list[int]:
+        n = len(srcs)
+        if len(sizes) != n or len(dsts) != n:
+            raise ValueError("srcs, sizes and dsts must have the same length")
+        P, Z = c_void_p * n, c_size_t * n
+        res = Z()
+        r = fn(self.ctx, n, bytesoftype, P(*[t.data_ptr() for t in srcs]), Z(*sizes), P(*[t.data_ptr() for t in dsts]), Z(*[t.numel() for t in dsts]), res,
+               self._stream_ptr())
+        self._check(r)
+        return list(res)
+
+    def compress_batch(self, srcs, bytesoftype: int, dsts) -> list[int]:
+        """srcs, dsts: lists of contiguous uint8 CUDA tensors, one frame per item in one pass of kernels.  Returns every item's
+        frame size or error code (ERROR_NAMES); raises StenosError only when the call as a whole fails."""
+        return self._batch(self.lib.stenos_hip_compress_batch, srcs, bytesoftype, [t.numel() for t in srcs], dsts)
+
+    def decompress_batch(self, frames, bytesoftype: int, csizes, dsts) -> list[int]:
+        """frames[i][:csizes[i]] -> dsts[i] for every item in one pass of kernels.  Returns every item's decompressed size or
+        error code; raises StenosError only when the call as a whole fails."""
+        return self._batch(self.lib.stenos_hip_decompress_batch, frames, bytesoftype, list(csizes), dsts)
