@@ -445,6 +445,8 @@ static size_t lz_decode(const uint8_t* in, size_t in_size, size_t T, uint8_t* ds
 		}
 		for (int j = 0; j < 8; ++j) {
 			if ((flag >> j) & 1) {
+				if (s == end) /* (the reference reads the distance without this test) */
+					return 0;
 				unsigned off = *s & 127u;
 				if (*s++ > 127u) {
 					if (s == end)

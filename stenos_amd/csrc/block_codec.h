@@ -1109,6 +1109,17 @@ WV_FN uint32_t encode_partial_lines(Lds lds, const Layout& L, uint32_t T, uint32
 
 constexpr uint32_t DEC_ERROR = 0xFFFFFFFFu;
 
+#ifdef WV_HOST_EMULATION
+// (tests: which form of the decoder a plane or a mini-LZ block took; counted by the host emulation only)
+enum DecForm { DEC_FORM_PACKED_PLAIN, DEC_FORM_PACKED_RAW, DEC_FORM_PACKED_RLE6, DEC_FORM_PACKED_RLE7, DEC_FORM_RUNS, DEC_FORM_SLOPES, DEC_FORM_GENERIC,
+	       DEC_FORM_LZ256, DEC_FORM_LZ256_EXACT, DEC_FORM_PLANES_TO, DEC_FORM_COUNT };
+inline uint64_t* emul_dec_form_counts()
+{
+	static uint64_t n[DEC_FORM_COUNT] = {};
+	return n;
+}
+#endif
+
 struct DecLayout {
 	uint32_t win;  // window of compressed bytes (+8 slack after the valid bytes)
 	uint32_t img;  // decoded block, element major, 256*T bytes
@@ -1214,6 +1225,9 @@ WV_FN void dec_write_lut(Lds lds, const DecLayout& L)
 template <bool has_raw, int has_rle> // has_rle: 0 no run-length rows, 1 of differences only (header 6), 2 of values too (header 7)
 WV_FN uint32_t decode_plane_packed(Lds lds, const DecLayout& L, uint32_t T, uint32_t j, uint32_t type, uint32_t cur, const U32& hdr, U32* keep)
 {
+#ifdef WV_HOST_EMULATION
+	++emul_dec_form_counts()[has_rle == 2 ? DEC_FORM_PACKED_RLE7 : has_rle ? DEC_FORM_PACKED_RLE6 : has_raw ? DEC_FORM_PACKED_RAW : DEC_FORM_PACKED_PLAIN];
+#endif
 	const U32 lane = lane_id_plain();
 	Lds win = lds + L.win;
 	const U32 row = lane >> 2, q = lane & 3u;
@@ -1380,6 +1394,7 @@ WV_FN uint32_t decode_plane_runs(Lds lds, const DecLayout& L, uint32_t T, uint32
 {
 #ifdef WV_HOST_EMULATION
 	++emul_plane_runs_count();
+	++emul_dec_form_counts()[DEC_FORM_RUNS];
 #endif
 	const U32 lane = lane_id_plain();
 	Lds win = lds + L.win;
@@ -1420,6 +1435,7 @@ WV_FN uint32_t decode_plane_slopes(Lds lds, const DecLayout& L, uint32_t T, uint
 {
 #ifdef WV_HOST_EMULATION
 	++emul_plane_runs_count(); // (the two short forms count together)
+	++emul_dec_form_counts()[DEC_FORM_SLOPES];
 #endif
 	const U32 lane = lane_id_plain();
 	Lds win = lds + L.win;
@@ -1488,6 +1504,9 @@ WV_FN uint32_t decode_plane(Lds lds, const DecLayout& L, uint32_t T, uint32_t j,
 		}
 		return decode_plane_packed<false, 0>(lds, L, T, j, type, cur, hdr, keep);
 	}
+#endif
+#ifdef WV_HOST_EMULATION
+	++emul_dec_form_counts()[DEC_FORM_GENERIC];
 #endif
 	if (type == PLANE_NORMAL) {
 		Pred emit = act & (hdr != U32(6u)) & (hdr != U32(7u)) & (hdr != U32(15u));
@@ -1721,6 +1740,9 @@ WV_FN uint32_t lz_decode_256(Lds lds, const DecLayout& L, uint32_t T, uint32_t c
 			p = readlane(at, 31) + 1 + 8 * B - (B - 1) * (uint32_t)__builtin_popcount(readlane(fl, 31));
 		}
 		else {
+#ifdef WV_HOST_EMULATION
+			++emul_dec_form_counts()[DEC_FORM_LZ256_EXACT];
+#endif
 			p = readlane(rec, first_long) & 0xFFFFu;
 			for (uint32_t g = first_long; g < 32; ++g) {
 				if (p + 2 > end)
@@ -1814,6 +1836,9 @@ WV_FN uint32_t lz_decode_256(Lds lds, const DecLayout& L, uint32_t T, uint32_t c
 			lds_st32(lds, a + 4u, vhi[k], match[k]);
 	}
 	wave_sync();
+#ifdef WV_HOST_EMULATION
+	++emul_dec_form_counts()[DEC_FORM_LZ256];
+#endif
 	return p - cur;
 }
 
@@ -1828,6 +1853,9 @@ WV_FN uint32_t decode_planes_to(Lds lds, const DecLayout& L, uint32_t cur, uint3
 	Lds win = lds + L.win;
 	uint32_t p = cur + header_bytes(T), bad = 0;
 	const uint32_t end = cur + avail;
+#ifdef WV_HOST_EMULATION
+	++emul_dec_form_counts()[DEC_FORM_PLANES_TO];
+#endif
 	U32 w[T];
 #ifndef WV_HOST_EMULATION
 #pragma unroll

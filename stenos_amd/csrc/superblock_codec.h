@@ -971,10 +971,24 @@ WV_FN BlockInfo encode_tail_job(Lds lds, const Layout& L, uint32_t T, const uint
 
 // ---- decode side -----------------------------------------------------------------------------------
 
+// the largest block an ENCODER writes (a block that would be longer is stored as a copy): sizes the encoders' staging runs
 WV_HD uint32_t max_block_bytes(uint32_t T) { return 256 * T + header_bytes(T) + 1; }
 WV_HD uint32_t max_tail_bytes(uint32_t T) { return 280 * T + header_bytes(T) + 2; }
-// window size: room for the largest block plus a few KiB so that small blocks are decoded several per refill
-WV_HD uint32_t window_bytes(uint32_t T) { return align16(max_tail_bytes(T) + 2048 + 32); }
+// The largest block the FORMAT allows, which is what a decoder has to take (the reference's does): every plane NORMAL_RLE
+// (8 header bytes, mask16 + 16 minimums) with sixteen run-length rows of sixteen literals each.  A copied block (1 + 256 * T)
+// and a mini-LZ block of literals only (1 + 256 * T + a flags byte per eight items of four or eight bytes) are shorter.
+WV_HD uint32_t max_stream_block_bytes(uint32_t T) { return header_bytes(T) + T * (8 + 18 + 16 * 18); }
+// ... and the largest tail: [254], planes of at most fifteen rows with a minimum byte each (no NORMAL_RLE there), then the raw
+// bytes behind the last whole row (fewer than 16 * T)
+WV_HD uint32_t max_stream_tail_bytes(uint32_t T) { return 1 + header_bytes(T) + T * (8 + 15 + 15 * 18) + 16 * T; }
+// window size: room for the largest block plus a few KiB so that small blocks are decoded several per refill; the window is
+// filled from a 16-byte boundary up to 15 bytes in front of the block, and the largest block of the format has to fit behind
+// them (it decides for bytesoftype 61 and more)
+WV_HD uint32_t window_bytes(uint32_t T)
+{
+	const uint32_t usual = max_tail_bytes(T) + 2048 + 32, largest = max_stream_block_bytes(T) + 16;
+	return align16(usual > largest ? usual : largest);
+}
 
 // The decoder checks the bytes a block consumed once per block, not before every read: a block whose first byte is in
 // the window reads at most hs + T*(8 + 18 + 16*18) + 16 bytes from there whatever the stream contains, so that much LDS
@@ -1056,7 +1070,7 @@ WV_FN uint32_t decode_superblock(Lds lds, const DecLayout& L, uint32_t T, const 
 	for (uint32_t b = 0; b < nblocks; ++b) {
 		WV_MARK("dec_block_begin");
 		uint32_t left = csize - consumed;
-		uint32_t need = left < max_block_bytes(T) ? left : max_block_bytes(T);
+		uint32_t need = left < max_stream_block_bytes(T) ? left : max_stream_block_bytes(T);
 		ensure(need);
 		WV_MARK("dec_block");
 		bool direct = false;
@@ -1076,7 +1090,7 @@ WV_FN uint32_t decode_superblock(Lds lds, const DecLayout& L, uint32_t T, const 
 		if (consumed == csize)
 			return DEC_ERROR;
 		uint32_t left = csize - consumed;
-		uint32_t need = left < max_tail_bytes(T) ? left : max_tail_bytes(T);
+		uint32_t need = left < max_stream_tail_bytes(T) ? left : max_stream_tail_bytes(T);
 		ensure(need);
 		uint32_t cur = consumed + mis - wstart;
 		if (win_u8(lds + L.win, cur) != BLOCK_PARTIAL)

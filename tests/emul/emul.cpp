@@ -17,12 +17,14 @@ typedef unsigned (*ze_fn)(size_t);
 
 using namespace codec;
 
+static int g_lds_fill = 0xCD; // what a wave finds in its LDS (emul_set_lds_fill: results must not depend on it)
+
 static uint8_t* alloc_lds(uint32_t bytes)
 {
 	void* p = nullptr;
 	if (posix_memalign(&p, 64, bytes + 256))
 		return nullptr;
-	memset(p, 0xCD, bytes + 256); // LDS is not zero-initialised on the device either
+	memset(p, g_lds_fill, bytes + 256); // LDS is not zero-initialised on the device either
 	return (uint8_t*)p;
 }
 
@@ -81,6 +83,69 @@ size_t emul_block_decompress(const uint8_t* src, size_t csize, size_t T, size_t 
 	free(lds);
 	return r == DEC_ERROR ? (size_t)-4 : r;
 }
+
+void emul_set_lds_fill(int byte) { g_lds_fill = byte & 255; }
+// planes and mini-LZ blocks the decoder forms of block_codec.h (enum DecForm) have taken so far
+size_t emul_dec_form_count(int form) { return form >= 0 && form < (int)DEC_FORM_COUNT ? (size_t)emul_dec_form_counts()[form] : (size_t)-1; }
+// the size limits of decode_superblock (superblock_codec.h): out = { largest block an encoder writes, largest block of the format, largest tail of the format }
+void emul_dec_limits(size_t T, uint32_t* out)
+{
+	out[0] = max_block_bytes((uint32_t)T);
+	out[1] = max_stream_block_bytes((uint32_t)T);
+	out[2] = max_stream_tail_bytes((uint32_t)T);
+}
+
+#ifdef WV_AUDIT
+// emul_block_decompress with every memory access of the kernel source checked (wavevec_host.h, "the access audit"):
+//   LDS           the wave's make_dec_layout(T).total bytes, nothing behind them;
+//   global reads  the 16-byte aligned hull of [src, src + csize): what copy_g2l may touch from the aligned address below src;
+//   global writes [dst, dst + dsize) exactly.
+// report = { violations, accesses checked, kind of the first violation (0 LDS, 1 global read, 2 global write), its offset from
+// the region's start (two's complement), its width }; its accessor's name: emul_audit_first_name().
+static const char* g_audit_first_name = "";
+const char* emul_audit_first_name(void) { return g_audit_first_name; }
+size_t emul_audit_block_decompress(const uint8_t* src, size_t csize, size_t T, size_t dsize, uint8_t* dst, int misalign, uint64_t* report)
+{
+	DecLayout L = make_dec_layout((uint32_t)T);
+	uint8_t* lds = nullptr;
+	uint8_t* in = nullptr;
+	uint8_t* out = nullptr;
+	// (the allocations are larger than the regions by a margin nothing relies on: an access outside a region does not take place)
+	if (posix_memalign((void**)&lds, 64, L.total + 64) || posix_memalign((void**)&in, 64, csize + 128) || posix_memalign((void**)&out, 64, dsize + 64))
+		return (size_t)-3;
+	memset(lds, g_lds_fill, L.total + 64);
+	memset(in, 0xEE, csize + 128);
+	memset(out, 0x5A, dsize + 64);
+	uint8_t* from = in + 16 + misalign;
+	memcpy(from, src, csize);
+	wv::AuditState& A = wv::audit_state();
+	memset(&A, 0, sizeof A);
+	A.lo[wv::WV_AUDIT_LDS] = lds;
+	A.hi[wv::WV_AUDIT_LDS] = lds + L.total;
+	A.lo[wv::WV_AUDIT_GREAD] = (const uint8_t*)((uintptr_t)from & ~(uintptr_t)15);
+	A.hi[wv::WV_AUDIT_GREAD] = (const uint8_t*)(((uintptr_t)from + csize + 15) & ~(uintptr_t)15);
+	A.lo[wv::WV_AUDIT_GWRITE] = out;
+	A.hi[wv::WV_AUDIT_GWRITE] = out + dsize;
+	A.on = true;
+	uint32_t r = decode_superblock(lds, L, (uint32_t)T, from, (uint32_t)csize, out, (uint32_t)dsize, g_dec_regs && (T == 2 || T == 4 || T == 8));
+	A.on = false;
+	report[0] = A.violations;
+	report[1] = A.checked;
+	report[2] = (uint64_t)A.first_kind;
+	report[3] = (uint64_t)A.first_off;
+	report[4] = A.first_width;
+	g_audit_first_name = A.first_name ? A.first_name : "";
+	for (size_t i = dsize; i < dsize + 64; ++i)
+		if (out[i] != 0x5A)
+			report[0] |= 1ull << 63; // (cannot happen: a store outside the region is suppressed)
+	if (r != DEC_ERROR)
+		memcpy(dst, out, dsize);
+	free(in);
+	free(out);
+	free(lds);
+	return r == DEC_ERROR ? (size_t)-4 : r;
+}
+#endif
 
 // The whole encode pipeline as capi.cpp enqueues it (encode_blocks, plan_superblocks, scan_superblocks,
 // resolve_frame, host zstd for a tiny last superblock, pack_frame), one "workgroup" after the other.

@@ -334,17 +334,83 @@ WV_FN U32 row_select4v(const U32& a0, const U32& a1, const U32& a2, const U32& a
 	return r;
 }
 
+// ---- the access audit (-DWV_AUDIT, the third build of tests/emul/Makefile) ----
+// Every accessor below goes through wv_ld / wv_st.  With WV_AUDIT, and while the harness has registered regions
+// (emul.cpp, emul_audit_*), an access is compared by absolute host address with the region of its kind -- the wave's LDS, the
+// bytes of global memory it may read, the bytes it may write --; one that leaves it is counted, the first one is recorded
+// (accessor, offset from the region's start, width) and it does not take place: a load gives 0.
+enum { WV_AUDIT_LDS = 0, WV_AUDIT_GREAD = 1, WV_AUDIT_GWRITE = 2 };
+#ifdef WV_AUDIT
+struct AuditState {
+	const uint8_t* lo[3];
+	const uint8_t* hi[3];
+	bool on;
+	uint64_t violations, checked;
+	const char* first_name;
+	int first_kind;
+	long long first_off;
+	uint32_t first_width;
+};
+inline AuditState& audit_state()
+{
+	static AuditState s = {};
+	return s;
+}
+WV_FN bool audit_ok(int kind, const char* name, const void* p, size_t n)
+{
+	AuditState& s = audit_state();
+	if (!s.on)
+		return true;
+	++s.checked;
+	const uint8_t* a = (const uint8_t*)p;
+	if (a >= s.lo[kind] && a <= s.hi[kind] && n <= (size_t)(s.hi[kind] - a))
+		return true;
+	if (!s.violations++) {
+		s.first_name = name;
+		s.first_kind = kind;
+		s.first_off = (long long)((intptr_t)a - (intptr_t)s.lo[kind]);
+		s.first_width = (uint32_t)n;
+	}
+	return false;
+}
+#else
+WV_FN bool audit_ok(int, const char*, const void*, size_t) { return true; }
+#endif
+WV_FN void wv_ld(int kind, const char* name, void* out, const uint8_t* p, size_t n)
+{
+	if (audit_ok(kind, name, p, n))
+		memcpy(out, p, n);
+	else
+		memset(out, 0, n);
+}
+WV_FN void wv_st(int kind, const char* name, uint8_t* p, const void* in, size_t n)
+{
+	if (audit_ok(kind, name, p, n))
+		memcpy(p, in, n);
+}
+WV_FN uint32_t wv_ld8(int kind, const char* name, const uint8_t* p)
+{
+	uint8_t v;
+	wv_ld(kind, name, &v, p, 1);
+	return v;
+}
+
 // ---- LDS (byte addressed; 32-bit accesses must be 4-byte aligned unless named *_unaligned) ----
 WV_FN U32 lds_ld8(Lds m, const U32& a)
 {
 	U32 r;
-	for (int i = 0; i < WAVE; ++i) r.l[i] = m[a.l[i]];
+	for (int i = 0; i < WAVE; ++i) r.l[i] = wv_ld8(WV_AUDIT_LDS, "lds_ld8", m + a.l[i]);
 	return r;
+}
+WV_FN uint32_t wv_ld16(const char* name, const uint8_t* p) // (two byte reads, as on the device)
+{
+	const uint32_t lo = wv_ld8(WV_AUDIT_LDS, name, p);
+	return lo | (wv_ld8(WV_AUDIT_LDS, name, p + 1) << 8);
 }
 WV_FN void lds_rle_walk_row(Lds m, uint32_t base, uint32_t first, U32& e, U32& mask) // (wavevec.h: one run-length row among rows of other kinds)
 {
 	const uint32_t at = base + e.l[first];
-	const uint32_t mk = (uint32_t)m[at] | ((uint32_t)m[at + 1] << 8);
+	const uint32_t mk = wv_ld16("lds_rle_walk_row", m + at);
 	for (int i = (int)first; i < WAVE; ++i)
 		mask.l[i] = mk;
 	for (int i = (int)first + 4; i < WAVE; ++i)
@@ -354,23 +420,19 @@ WV_FN void lds_lz_walk32(Lds m, U32& at, U32& flags, uint32_t B) // (wavevec.h: 
 {
 	uint32_t a = at.l[0];
 	for (int g = 0; g < 32; ++g) {
-		const uint32_t fl = m[a];
-		for (int i = g; i < (g == 31 ? 32 : g + 1); ++i) {
+		const uint32_t fl = wv_ld8(WV_AUDIT_LDS, "lds_lz_walk32", m + a);
+		for (int i = g; i < (g == 31 ? WAVE : g + 1); ++i) { // (lanes 32-63 keep what lane 31 holds: the device walk ends with group 31)
 			at.l[i] = a;
 			flags.l[i] = fl;
 		}
 		a += 1 + 8 * B - (B - 1) * (uint32_t)__builtin_popcount(fl);
-	}
-	for (int i = 32; i < WAVE; ++i) { // (one step on; not used)
-		at.l[i] = a;
-		flags.l[i] = m[a];
 	}
 }
 WV_FN void lds_rle_walk16(Lds m, U32& at, U32& mask) // (wavevec.h: sixteen run-length rows in a chain, the lane's row's offset and mask)
 {
 	uint32_t a = at.l[0];
 	for (int r = 0; r < 16; ++r) {
-		const uint32_t mk = (uint32_t)m[a] | ((uint32_t)m[a + 1] << 8);
+		const uint32_t mk = wv_ld16("lds_rle_walk16", m + a);
 		for (int i = 4 * r; i < 4 * r + 4; ++i) {
 			at.l[i] = a;
 			mask.l[i] = mk;
@@ -381,25 +443,30 @@ WV_FN void lds_rle_walk16(Lds m, U32& at, U32& mask) // (wavevec.h: sixteen run-
 WV_FN U32 lds_ld32(Lds m, const U32& a)
 {
 	U32 r;
-	for (int i = 0; i < WAVE; ++i) memcpy(&r.l[i], m + (a.l[i] & ~3u), 4);
+	for (int i = 0; i < WAVE; ++i) wv_ld(WV_AUDIT_LDS, "lds_ld32", &r.l[i], m + (a.l[i] & ~3u), 4);
 	return r;
 }
 WV_FN void lds_ld64(Lds m, const U32& a, U32& lo, U32& hi)
 {
 	for (int i = 0; i < WAVE; ++i) {
-		memcpy(&lo.l[i], m + (a.l[i] & ~3u), 4);
-		memcpy(&hi.l[i], m + (a.l[i] & ~3u) + 4, 4);
+		uint32_t v[2];
+		wv_ld(WV_AUDIT_LDS, "lds_ld64", v, m + (a.l[i] & ~3u), 8);
+		lo.l[i] = v[0];
+		hi.l[i] = v[1];
 	}
 }
 WV_FN void lds_st32(Lds m, const U32& a, const U32& v, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
-		if (p.l[i]) memcpy(m + (a.l[i] & ~3u), &v.l[i], 4);
+		if (p.l[i]) wv_st(WV_AUDIT_LDS, "lds_st32", m + (a.l[i] & ~3u), &v.l[i], 4);
 }
 WV_FN void lds_st8(Lds m, const U32& a, const U32& v, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
-		if (p.l[i]) m[a.l[i]] = (uint8_t)v.l[i];
+		if (p.l[i]) {
+			const uint8_t b = (uint8_t)v.l[i];
+			wv_st(WV_AUDIT_LDS, "lds_st8", m + a.l[i], &b, 1);
+		}
 }
 // atomic add returning the previous value (lane order on the host; any order is a valid device order)
 WV_FN U32 lds_add_rtn32(Lds m, const U32& a, const U32& v, const Pred& p)
@@ -408,10 +475,10 @@ WV_FN U32 lds_add_rtn32(Lds m, const U32& a, const U32& v, const Pred& p)
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
 			uint32_t t;
-			memcpy(&t, m + (a.l[i] & ~3u), 4);
+			wv_ld(WV_AUDIT_LDS, "lds_add_rtn32", &t, m + (a.l[i] & ~3u), 4);
 			r.l[i] = t;
 			t += v.l[i];
-			memcpy(m + (a.l[i] & ~3u), &t, 4);
+			wv_st(WV_AUDIT_LDS, "lds_add_rtn32", m + (a.l[i] & ~3u), &t, 4);
 		}
 	return r;
 }
@@ -422,9 +489,9 @@ WV_FN U32 lds_cas32(Lds m, const U32& a, const U32& expect, const U32& v, const 
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
 			uint32_t t;
-			memcpy(&t, m + (a.l[i] & ~3u), 4);
+			wv_ld(WV_AUDIT_LDS, "lds_cas32", &t, m + (a.l[i] & ~3u), 4);
 			r.l[i] = t;
-			if (t == expect.l[i]) memcpy(m + (a.l[i] & ~3u), &v.l[i], 4);
+			if (t == expect.l[i]) wv_st(WV_AUDIT_LDS, "lds_cas32", m + (a.l[i] & ~3u), &v.l[i], 4);
 		}
 	return r;
 }
@@ -434,10 +501,10 @@ WV_FN U32 lds_or_rtn32(Lds m, const U32& a, const U32& v)
 	U32 r;
 	for (int i = 0; i < WAVE; ++i) {
 		uint32_t t;
-		memcpy(&t, m + a.l[i], 4);
+		wv_ld(WV_AUDIT_LDS, "lds_or_rtn32", &t, m + a.l[i], 4);
 		r.l[i] = t;
 		t |= v.l[i];
-		memcpy(m + a.l[i], &t, 4);
+		wv_st(WV_AUDIT_LDS, "lds_or_rtn32", m + a.l[i], &t, 4);
 	}
 	return r;
 }
@@ -446,9 +513,9 @@ WV_FN void lds_or32_all(Lds m, const U32& a, const U32& v)
 {
 	for (int i = 0; i < WAVE; ++i) {
 		uint32_t t;
-		memcpy(&t, m + a.l[i], 4);
+		wv_ld(WV_AUDIT_LDS, "lds_or32_all", &t, m + a.l[i], 4);
 		t |= v.l[i];
-		memcpy(m + a.l[i], &t, 4);
+		wv_st(WV_AUDIT_LDS, "lds_or32_all", m + a.l[i], &t, 4);
 	}
 }
 WV_FN void lds_or32(Lds m, const U32& a, const U32& v, const Pred& p)
@@ -456,9 +523,9 @@ WV_FN void lds_or32(Lds m, const U32& a, const U32& v, const Pred& p)
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
 			uint32_t t;
-			memcpy(&t, m + (a.l[i] & ~3u), 4);
+			wv_ld(WV_AUDIT_LDS, "lds_or32", &t, m + (a.l[i] & ~3u), 4);
 			t |= v.l[i];
-			memcpy(m + (a.l[i] & ~3u), &t, 4);
+			wv_st(WV_AUDIT_LDS, "lds_or32", m + (a.l[i] & ~3u), &t, 4);
 		}
 }
 
@@ -470,21 +537,23 @@ WV_FN U32 gld8(const uint8_t* g, const U32& off, const Pred& p)
 {
 	U32 r(0u);
 	for (int i = 0; i < WAVE; ++i)
-		if (p.l[i]) r.l[i] = g[off.l[i]];
+		if (p.l[i]) r.l[i] = wv_ld8(WV_AUDIT_GREAD, "gld8", g + off.l[i]);
 	return r;
 }
 WV_FN U32 gld32(const uint8_t* g, const U32& off, const Pred& p) // off multiple of 4, g 4-byte aligned
 {
 	U32 r(0u);
 	for (int i = 0; i < WAVE; ++i)
-		if (p.l[i]) memcpy(&r.l[i], g + off.l[i], 4);
+		if (p.l[i]) wv_ld(WV_AUDIT_GREAD, "gld32", &r.l[i], g + off.l[i], 4);
 	return r;
 }
 WV_FN void gld64(const uint8_t* g, const U32& off, U32& lo, U32& hi) // 8-byte aligned, all lanes
 {
 	for (int i = 0; i < WAVE; ++i) {
-		memcpy(&lo.l[i], g + off.l[i], 4);
-		memcpy(&hi.l[i], g + off.l[i] + 4, 4);
+		uint32_t v[2];
+		wv_ld(WV_AUDIT_GREAD, "gld64", v, g + off.l[i], 8);
+		lo.l[i] = v[0];
+		hi.l[i] = v[1];
 	}
 }
 WV_FN U128 gld128(const uint8_t* g, const U32& off, const Pred& p) // 16-byte aligned
@@ -493,10 +562,9 @@ WV_FN U128 gld128(const uint8_t* g, const U32& off, const Pred& p) // 16-byte al
 	r.x = r.y = r.z = r.w = U32(0u);
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
-			memcpy(&r.x.l[i], g + off.l[i], 4);
-			memcpy(&r.y.l[i], g + off.l[i] + 4, 4);
-			memcpy(&r.z.l[i], g + off.l[i] + 8, 4);
-			memcpy(&r.w.l[i], g + off.l[i] + 12, 4);
+			uint32_t v[4];
+			wv_ld(WV_AUDIT_GREAD, "gld128", v, g + off.l[i], 16);
+			r.x.l[i] = v[0], r.y.l[i] = v[1], r.z.l[i] = v[2], r.w.l[i] = v[3];
 		}
 	return r;
 }
@@ -506,29 +574,30 @@ WV_FN void gld64_unaligned(const uint8_t* g, const U32& off, U32& lo, U32& hi) {
 WV_FN void gst8(uint8_t* g, const U32& off, const U32& v, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
-		if (p.l[i]) g[off.l[i]] = (uint8_t)v.l[i];
+		if (p.l[i]) {
+			const uint8_t b = (uint8_t)v.l[i];
+			wv_st(WV_AUDIT_GWRITE, "gst8", g + off.l[i], &b, 1);
+		}
 }
 WV_FN void gst32(uint8_t* g, const U32& off, const U32& v, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
-		if (p.l[i]) memcpy(g + off.l[i], &v.l[i], 4);
+		if (p.l[i]) wv_st(WV_AUDIT_GWRITE, "gst32", g + off.l[i], &v.l[i], 4);
 }
 WV_FN void gst64(uint8_t* g, const U32& off, const U32& lo, const U32& hi, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
-			memcpy(g + off.l[i], &lo.l[i], 4);
-			memcpy(g + off.l[i] + 4, &hi.l[i], 4);
+			const uint32_t v[2] = { lo.l[i], hi.l[i] };
+			wv_st(WV_AUDIT_GWRITE, "gst64", g + off.l[i], v, 8);
 		}
 }
 WV_FN void gst128(uint8_t* g, const U32& off, const U128& v, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
-			memcpy(g + off.l[i], &v.x.l[i], 4);
-			memcpy(g + off.l[i] + 4, &v.y.l[i], 4);
-			memcpy(g + off.l[i] + 8, &v.z.l[i], 4);
-			memcpy(g + off.l[i] + 12, &v.w.l[i], 4);
+			const uint32_t w[4] = { v.x.l[i], v.y.l[i], v.z.l[i], v.w.l[i] };
+			wv_st(WV_AUDIT_GWRITE, "gst128", g + off.l[i], w, 16);
 		}
 }
 WV_FN void gst128_unaligned(uint8_t* g, const U32& off, const U128& v, const Pred& p) { gst128(g, off, v, p); }
@@ -539,24 +608,37 @@ WV_FN void gst128_through(uint8_t* g, const U32& off, const U128& v) { gst128(g,
 WV_FN void gst64_through(uint8_t* g, const U32& off, const U32& lo, const U32& hi) { gst64(g, off, lo, hi, pred_all(true)); }
 WV_FN void gst_through_wait() {}
 // wave-uniform scalar accesses to global memory
-WV_FN uint32_t gload_uniform(const uint32_t* p) { return *p; }
-WV_FN uint32_t gload_uniform8(const uint8_t* p) { return *p; }
-WV_FN uint64_t gload_uniform64(const uint64_t* p) { return *p; }
-WV_FN void gstore_uniform(uint32_t* p, uint32_t v) { *p = v; }
-WV_FN void gstore_uniform8(uint8_t* p, uint32_t v) { *p = (uint8_t)v; }
-WV_FN void gstore_uniform64(uint64_t* p, uint64_t v) { *p = v; }
+WV_FN uint32_t gload_uniform(const uint32_t* p)
+{
+	uint32_t v;
+	wv_ld(WV_AUDIT_GREAD, "gload_uniform", &v, (const uint8_t*)p, 4);
+	return v;
+}
+WV_FN uint32_t gload_uniform8(const uint8_t* p) { return wv_ld8(WV_AUDIT_GREAD, "gload_uniform8", p); }
+WV_FN uint64_t gload_uniform64(const uint64_t* p)
+{
+	uint64_t v;
+	wv_ld(WV_AUDIT_GREAD, "gload_uniform64", &v, (const uint8_t*)p, 8);
+	return v;
+}
+WV_FN void gstore_uniform(uint32_t* p, uint32_t v) { wv_st(WV_AUDIT_GWRITE, "gstore_uniform", (uint8_t*)p, &v, 4); }
+WV_FN void gstore_uniform8(uint8_t* p, uint32_t v)
+{
+	const uint8_t b = (uint8_t)v;
+	wv_st(WV_AUDIT_GWRITE, "gstore_uniform8", p, &b, 1);
+}
+WV_FN void gstore_uniform64(uint64_t* p, uint64_t v) { wv_st(WV_AUDIT_GWRITE, "gstore_uniform64", (uint8_t*)p, &v, 8); }
 WV_FN void gmin32(uint32_t* p, uint32_t v)
 {
-	if (v < *p) *p = v;
+	if (v < gload_uniform(p)) gstore_uniform(p, v);
 }
 WV_FN U128 lds_ld128(Lds m, const U32& a) // 16-byte aligned
 {
 	U128 r;
 	for (int i = 0; i < WAVE; ++i) {
-		memcpy(&r.x.l[i], m + a.l[i], 4);
-		memcpy(&r.y.l[i], m + a.l[i] + 4, 4);
-		memcpy(&r.z.l[i], m + a.l[i] + 8, 4);
-		memcpy(&r.w.l[i], m + a.l[i] + 12, 4);
+		uint32_t v[4];
+		wv_ld(WV_AUDIT_LDS, "lds_ld128", v, m + a.l[i], 16);
+		r.x.l[i] = v[0], r.y.l[i] = v[1], r.z.l[i] = v[2], r.w.l[i] = v[3];
 	}
 	return r;
 }
@@ -564,10 +646,8 @@ WV_FN void lds_st128(Lds m, const U32& a, const U128& v, const Pred& p)
 {
 	for (int i = 0; i < WAVE; ++i)
 		if (p.l[i]) {
-			memcpy(m + a.l[i], &v.x.l[i], 4);
-			memcpy(m + a.l[i] + 4, &v.y.l[i], 4);
-			memcpy(m + a.l[i] + 8, &v.z.l[i], 4);
-			memcpy(m + a.l[i] + 12, &v.w.l[i], 4);
+			const uint32_t w[4] = { v.x.l[i], v.y.l[i], v.z.l[i], v.w.l[i] };
+			wv_st(WV_AUDIT_LDS, "lds_st128", m + a.l[i], w, 16);
 		}
 }
 

@@ -187,6 +187,9 @@ def test_decoder_lds_covers_the_reach_of_an_unchecked_block(emul):
         assert total >= wcap + reach, T          # a block starting at the window's last byte stays inside
         assert total >= img + 256 * T, T         # the decoded block
         assert total <= 64 * 1024, T             # one workgroup's limit
+        # the longest block the format allows (every plane NORMAL_RLE, sixteen run-length rows of sixteen literals) fits the
+        # window behind the up to 15 bytes between the 16-byte boundary the window starts at and the block
+        assert wcap >= hs + T * (8 + 18 + 16 * 18) + 15, T
 
 
 @pytest.mark.parametrize("T", [2, 4])
