@@ -7,7 +7,7 @@
 #pragma once
 #include "kernels.h"
 
-// per-item words of a compress batch (device): what enqueue_compress keeps at misc + 0, + 12, + 16
+// per-item words of a compress batch (device): what enqueue_compress keeps in DeviceWords (host.h): total, encode_status, first_flagged
 struct BatchItemState {
 	uint64_t total;
 	uint32_t status;

@@ -147,7 +147,7 @@ size_t emul_audit_block_decompress(const uint8_t* src, size_t csize, size_t T, s
 }
 #endif
 
-// The whole encode pipeline as capi.cpp enqueues it (encode_blocks, plan_superblocks, scan_superblocks,
+// The whole encode pipeline as encode_host.cpp enqueues it (encode_blocks, plan_superblocks, scan_superblocks,
 // resolve_frame, host zstd for a tiny last superblock, pack_frame), one "workgroup" after the other.
 
 static int g_fused = 1;
@@ -233,7 +233,7 @@ size_t emul_compress_frame(const uint8_t* src_in, size_t T, size_t bytes, uint8_
 	j.check_total = 1;
 	Layout L = make_layout((uint32_t)T, true);
 	uint8_t* lds = alloc_lds(L.total);
-	// fused zone (capi.cpp enqueue_compress): leading superblocks of full blocks with room for any encoding
+	// fused zone (encode_host.cpp enqueue_compress): leading superblocks of full blocks with room for any encoding
 	uint64_t s_tight = safe_superblocks(dst_size, j.header_bytes, j.bps, j.T, sb, j.nsb);
 	if (j.tiny_last && s_tight > j.nsb - 1)
 		s_tight = j.nsb - 1;

@@ -88,7 +88,7 @@ def test_wide_copy_any_alignment(emul):
 @pytest.mark.parametrize("T", [2, 4, 8, 3, 12])
 def test_frame_pipeline_and_capacity_rules(oracle, emul, T, fused):
     """The whole encode pipeline (encode_superblocks for the leading superblocks with ample room, then
-    encode_blocks, plan, scan, resolve, pack, as capi.cpp enqueues them; fused=0: without the fused
+    encode_blocks, plan, scan, resolve, pack, as encode_host.cpp enqueues them; fused=0: without the fused
     kernel) against the oracle's serial path for dst_size = bound, larger, and smaller: same frame or
     both an error.  Covers the reference's capacity-dependent LZ attempt (block_compress.h:1214) and
     dst_end tests (:1225, 1241, 1284) that decide BLOCK vs COPY near the end of the buffer."""

@@ -195,7 +195,7 @@ def test_decode_mixed_batches(T):
             csizes.append(fr.nbytes)
             dsts.append(torch.zeros(_input(e).nbytes, dtype=torch.uint8, device="cuda"))
             want.append(_input(e))
-        for k, n in enumerate([300 * _sb(T) + 5, 1000 * T + 3, 3 * _sb(T) + 11]):  # (300 superblocks: the parallel walk, capi.cpp)
+        for k, n in enumerate([300 * _sb(T) + 5, 1000 * T + 3, 3 * _sb(T) + 11]):  # (300 superblocks: the parallel walk, batch_host.cpp)
             d = _data("walk", T, n, 5 + k)
             f = torch.empty(st.bound(n), dtype=torch.uint8, device="cuda")
             r = st.compress(torch.from_numpy(d).cuda(), T, f)

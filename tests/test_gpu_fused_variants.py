@@ -1,5 +1,5 @@
 """The two fused encoders of bytesoftype 4 (kernels.hip): encode_superblocks, ordinary accesses and eight workgroups per CU, and
-encode_superblocks_nt, non-temporal input and frame and fewer workgroups.  The library picks one per call (capi.cpp: the nt
+encode_superblocks_nt, non-temporal input and frame and fewer workgroups.  The library picks one per call (encode_host.cpp: the nt
 kernel unless the context's last fused call stored more than half its superblocks as copies); the test build can force either
 (stenos_hip_test_fused_timeouts(ctx, -1 - v)).  Both must write the oracle's frame byte for byte whatever the data: 12-bit
 values, full entropy, copies and coded superblocks in every alternation, more superblocks than resident workgroups, and a

@@ -1,4 +1,4 @@
-"""Host-pointer calls on several devices (capi.cpp, compress_lanes / decompress_lanes): after stenos_hip_set_devices(ctx, n)
+"""Host-pointer calls on several devices (host_pointer.cpp, compress_lanes / decompress_lanes): after stenos_hip_set_devices(ctx, n)
 a call with stenos_set_threads(ctx, n) uses up to n devices, each taking a contiguous range of superblocks through a child
 context on a host thread of its own (reference dispatcher: stenos.cpp:909-1010, 1151-1202).  The test box has ONE GPU, so
 the lanes share it (stenos_hip_test_lanes): what is checked is the orchestration -- the frame must be byte-identical to

@@ -238,7 +238,7 @@ def test_small_custom_superblocks_exceed_stenos_bound(lib, ref_det):
 @pytest.mark.parametrize("T,kind,n,shift", [(4, "mixed", 30_000_011, None), (2, "walk", 60_000_001, None), (8, "lzmix", 13_000_003, 3), (4, "rand", 26_000_000, None)])
 def test_chunked_host_calls(lib, oracle, T, kind, n, shift):
     """Host-pointer calls of 96 MiB and more are cut into chunks of whole superblocks whose uploads overlap the coding and
-    the downloads (capi.cpp::compress_chunked / decompress_chunked): same frame as a single pass, tight destinations
+    the downloads (host_pointer.cpp::compress_chunked / decompress_chunked): same frame as a single pass, tight destinations
     included, and the same bytes back."""
     c = lib.stenos_make_context()
     if shift is not None:

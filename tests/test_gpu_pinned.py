@@ -1,4 +1,4 @@
-"""Host-pointer calls on page-locked memory (capi.cpp, device_alias): when the caller's source and / or destination are
+"""Host-pointer calls on page-locked memory (host_pointer.cpp, device_alias): when the caller's source and / or destination are
 page-locked (hipHostMalloc, hipHostRegister, a pinned tensor) the kernels read and write them through the link instead of
 staging a copy in device memory.  Same frames, same decoded bytes, nothing written past the destination."""
 import numpy as np

@@ -115,7 +115,7 @@ def large_row(st):
 def walk_rows():
     """Decode time of a single call on a frame of k superblocks (int32) that comes without an index: the serial walk by one lane
     against the parallel walk.  In a decode batch every item's serial walk runs at the same time on a lane of its own, while the
-    parallel walk is one launch per item (capi.cpp, kBatchSerialWalkMax)."""
+    parallel walk is one launch per item (batch_host.cpp, kBatchSerialWalkMax)."""
     from stenos_amd.api import load_library
 
     lib = load_library(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "hooks", "libstenos_hooks.so"))
