@@ -38,14 +38,16 @@ STENOS_EXPORT size_t stenos_hip_compress_async(stenos_context* ctx, const void* 
 STENOS_EXPORT size_t stenos_hip_finish(stenos_context* ctx);
 
 /* Superblock index of the last compression on ctx: device array of nsb + 1 uint64 byte offsets of the
- * superblock headers inside the frame (the last entry is the frame size).  Valid until the next call on ctx. */
+ * superblock headers inside the frame (the last entry is the frame size).  Valid until the next call on ctx;
+ * stenos_hip_decompress_ranges calls that are given this pointer leave it as it is, any number of them. */
 STENOS_EXPORT const uint64_t* stenos_hip_last_index(stenos_context* ctx, size_t* nsb);
 
 /* Superblock index of any frame held in device memory: the chain of [code][csize:3] headers (reference
  * stenos.cpp:1126-1134, 1166-1182) is walked on the device -- by segments of the frame in parallel, with a result that is
  * proven equal to the serial walk's before it is used (csrc/walk.h).  Returns a device array of *nsb + 1 uint64 byte offsets
- * (the last entry is the end of the last superblock), valid until the next call on ctx; NULL for an empty,
- * malformed or truncated frame.  Waits for the walk.  What a multi-GPU decoder cuts the frame with. */
+ * (the last entry is the end of the last superblock), valid until the next call on ctx; NULL for an empty, malformed or
+ * truncated frame.  stenos_hip_decompress_ranges calls that are given this pointer leave it as it is, any number of them.
+ * Waits for the walk.  What a multi-GPU decoder cuts the frame with. */
 STENOS_EXPORT const uint64_t* stenos_hip_frame_index(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t* nsb, void* stream);
 
 /* Decompress a frame held in device memory.  d_index may be NULL: the superblock chain
@@ -80,6 +82,36 @@ STENOS_EXPORT size_t stenos_hip_decompress_batch(stenos_context* ctx, size_t n, 
 /* Device workspace a compress batch of these n sizes needs (capacity planning, like stenos_hip_workspace_bytes); 0 for a
  * bytesoftype outside 1..64. */
 STENOS_EXPORT size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t n, const size_t* bytes);
+
+/* Random access: n byte ranges of the ORIGINAL array out of one frame in device memory, without inflating the rest: bytes
+ * [offsets[i], offsets[i] + lengths[i]) go to d_dsts[i][0 .. lengths[i]).  offsets, lengths, d_dsts: host arrays of n.
+ * Ranges are in bytes: any offset, any length (0 allowed: nothing is delivered, d_dsts[i] is not looked at), any alignment of
+ * d_dsts[i].  Ranges may overlap or repeat in the source; destinations must not overlap each other.  Returns the sum of the
+ * lengths, or an error code for the call as a whole; n == 0 returns 0.  Nothing is ever written outside
+ * [d_dsts[i], d_dsts[i] + lengths[i]), neither on success nor on any error.  Waits for completion (there is no _async form).
+ * Refused on the host, before any launch, with nothing written:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        a range with offset + length beyond the array's size (the frame header's, parsed as
+ *                                         stenos_hip_decompress parses it; the sum is not formed, it may wrap), bytesoftype
+ *                                         outside 1..64, more than 2^31 - 1 pieces (below), or while an _async job on ctx is
+ *                                         unfinished (that job is left alone);
+ *   a frame header stenos_hip_decompress refuses: its error code.
+ * d_index is as for stenos_hip_decompress: NULL has the chain walked first (into the context's own index); an index that is
+ * given is used as it is.  It may be the context's own, from stenos_hip_frame_index / stenos_hip_last_index: this call leaves
+ * that buffer intact (its tables live in a buffer of their own), so the intended use is to index a frame once and read ranges
+ * many times with the same pointer.
+ * Every range is cut at the frame's superblock boundaries and one wavefront delivers each piece; pieces that share a superblock
+ * are decoded each on its own, nothing is merged.  A superblock is a chain of blocks that has to be parsed from its start, so a
+ * piece costs the decoding of its superblock up to the block that holds its last byte; a piece that is a whole superblock takes
+ * the path of stenos_hip_decompress.  The number of launches and host round trips does not depend on n.
+ * WHAT IS CHECKED: only the superblocks a range touches are read, and of those only the blocks up to the last byte asked
+ * for.  Damage anywhere else in the frame is NOT detected by this call (with d_index == NULL the walk still sees every
+ * superblock header).  A truncated or malformed superblock or block that is decoded gives STENOS_ERROR_SRC_OVERFLOW /
+ * STENOS_ERROR_INVALID_INPUT as in stenos_hip_decompress; destinations may then be partly written, inside their bounds.
+ * Superblocks with zstd-based codes (every superblock of a level >= 2 frame and of bytesoftype 1, the last superblock under
+ * 128 bytes of a level-1 frame) are fetched and inflated on the host piece by piece, which is slow. */
+STENOS_EXPORT size_t stenos_hip_decompress_ranges(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t n, const uint64_t* offsets,
+						  const uint64_t* lengths, void* const* d_dsts, const uint64_t* d_index, void* stream);
 
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),

@@ -92,6 +92,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_delta_inv": (sz, [vp, vp, sz, vp]),
         "stenos_hip_compress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_decompress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
+        "stenos_hip_decompress_ranges": (sz, [vp, vp, sz, sz, sz, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64), ctypes.POINTER(vp), vp, vp]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
@@ -214,3 +215,20 @@ class Stenos:
         """frames[i][:csizes[i]] -> dsts[i] for every item in one pass of kernels.  Returns every item's decompressed size or
         error code; raises StenosError only when the call as a whole fails."""
         return self._batch(self.lib.stenos_hip_decompress_batch, frames, bytesoftype, list(csizes), dsts)
+
+    def decompress_ranges(self, frame, bytesoftype: int, csize: int, ranges, dsts, index_ptr: int | None = None) -> int:
+        """Bytes [offset, offset + length) of the ORIGINAL array, for every (offset, length) of `ranges`, out of frame[:csize] into
+        dsts[i][:length] in one call (dsts: contiguous uint8 CUDA tensors that do not overlap, or raw device addresses).  Only the
+        superblocks a range touches are read.  index_ptr: as for decompress; the pointer of frame_index / last_index may be
+        passed to any number of these calls.  Returns the bytes delivered."""
+        n = len(ranges)
+        if len(dsts) != n:
+            raise ValueError("ranges and dsts must have the same length")
+        U, P = c_uint64 * n, c_void_p * n
+        offs, lens = U(*[int(o) for o, _ in ranges]), U(*[int(l) for _, l in ranges])
+        ptrs = P(*[d if isinstance(d, int) else d.data_ptr() for d in dsts])
+        return self._check(self.lib.stenos_hip_decompress_ranges(self.ctx, frame.data_ptr(), bytesoftype, csize, n, offs, lens, ptrs, index_ptr, self._stream_ptr()))
+
+    def decompress_range(self, frame, bytesoftype: int, csize: int, offset: int, length: int, dst, index_ptr: int | None = None) -> int:
+        """One range: bytes [offset, offset + length) of the original array -> dst[:length]."""
+        return self.decompress_ranges(frame, bytesoftype, csize, [(offset, length)], [dst], index_ptr)

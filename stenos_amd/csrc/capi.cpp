@@ -442,6 +442,17 @@ size_t stenos_hip_decompress_batch(stenos_context* ctx, size_t n, size_t bytesof
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return decompress_batch(ctx, n, bytesoftype, d_srcs, src_sizes, d_dsts, dst_sizes, results, (hipStream_t)stream);
 }
+size_t stenos_hip_decompress_ranges(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t n, const uint64_t* offsets,
+				    const uint64_t* lengths, void* const* d_dsts, const uint64_t* d_index, void* stream)
+{
+	if (n == 0)
+		return 0;
+	if (!ctx || !d_src || !offsets || !lengths || !d_dsts)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return decompress_ranges(ctx, d_src, bytesoftype, bytes, n, offsets, lengths, d_dsts, d_index, (hipStream_t)stream);
+}
 size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t n, const size_t* bytes)
 {
 	if (bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || (n && !bytes))
