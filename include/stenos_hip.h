@@ -113,6 +113,46 @@ STENOS_EXPORT size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t
 STENOS_EXPORT size_t stenos_hip_decompress_ranges(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t n, const uint64_t* offsets,
 						  const uint64_t* lengths, void* const* d_dsts, const uint64_t* d_index, void* stream);
 
+/* Gather: n rows of the ORIGINAL array out of one frame in device memory, by row numbers that live in DEVICE memory.  Row r is
+ * bytes [r * row_bytes, (r + 1) * row_bytes) of the array; row d_rows[i] goes to d_dst + i * dst_stride, for i in 0..n.  The
+ * host never reads d_rows on the common path, and every enqueued step is ordered on `stream`: row numbers written by earlier
+ * work on that stream (a kernel, a torch op) need no synchronisation by the caller.  row_bytes >= 1 may be any value (not a
+ * multiple of bytesoftype, larger than a superblock), d_dst may have any alignment, dst_stride >= row_bytes; rows may repeat,
+ * in any order.  Returns n * row_bytes, or an error code for the call as a whole; n == 0 returns 0 before the devices are
+ * looked at.  Nothing is ever written outside the n slots [d_dst + i * dst_stride, + row_bytes) -- nothing in the dst_stride -
+ * row_bytes bytes between them either --, neither on success nor on any error.  Waits for completion (there is no _async form).
+ * Refused on the host, before any launch, with nothing written:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        row_bytes == 0, dst_stride < row_bytes, n * row_bytes or (n - 1) * dst_stride +
+ *                                         row_bytes not representable, bytesoftype outside 1..64, more than 2^31 - 1 pieces
+ *                                         (n times the pieces per row, below), or while an _async job on ctx is unfinished
+ *                                         (that job is left alone);
+ *   a frame header stenos_hip_decompress refuses: its error code.
+ * ROW NUMBERS ARE CHECKED ON THE DEVICE: a valid row has d_rows[i] < floor(array size / row_bytes) (the host computes that
+ * bound, no product that may wrap is formed on the device).  An invalid row makes no piece -- its slot is not touched -- and the
+ * call then returns STENOS_ERROR_INVALID_PARAMETER, in front of any decode error; what the other slots hold after that return
+ * is unspecified.
+ * d_index is as for stenos_hip_decompress_ranges: NULL has the chain walked first (into the context's own index); an index that
+ * is given is used as it is.  It may be the context's own, from stenos_hip_frame_index / stenos_hip_last_index: this call leaves
+ * that buffer intact (its tables live in a buffer of their own), any number of calls.
+ * Every row is cut at the frame's superblock boundaries on the device -- a fixed number of pieces per row: 1 when row_bytes
+ * divides the superblock size, else ceil((row_bytes - 1) / superblock size) + 1, some of them empty --, the pieces are
+ * grouped by superblock there, and one wavefront walks a superblock's chain of blocks once for up to 64 of its pieces, up to
+ * the block that holds the last byte any of them asks for.  The number of launches and host round trips depends neither on n
+ * nor on the number of superblocks: at most min(superblocks, pieces) + pieces / 64 wavefronts decode.  Pieces that cover a
+ * whole superblock take the same path through the wavefront's LDS image: a caller with rows of a superblock or more is better
+ * served by stenos_hip_decompress_ranges.  A single row costs four launches where the ranges call has one and is slower than
+ * it (profiles/gather_rate.txt).
+ * WHAT IS CHECKED: only the superblocks a row touches are read, and of those only the blocks up to the last byte asked
+ * for.  Damage anywhere else in the frame is NOT detected by this call (with d_index == NULL the walk still sees every
+ * superblock header).  A truncated or malformed superblock or block that is decoded gives STENOS_ERROR_SRC_OVERFLOW /
+ * STENOS_ERROR_INVALID_INPUT as in stenos_hip_decompress; slots may then be partly written, inside their bounds.
+ * Superblocks with zstd-based codes (every superblock of a level >= 2 frame and of bytesoftype 1, the last superblock under
+ * 128 bytes of a level-1 frame) are finished on the host: d_rows comes down, the pieces of those superblocks are cut again
+ * there and inflated piece by piece, which is slow. */
+STENOS_EXPORT size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n,
+					    const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream);
+
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),
  * byte delta in four quarter streams above 2048 bytes and its inverse.  src and dst must not overlap.

@@ -93,6 +93,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_compress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_decompress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_decompress_ranges": (sz, [vp, vp, sz, sz, sz, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64), ctypes.POINTER(vp), vp, vp]),
+        "stenos_hip_gather_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
@@ -232,3 +233,19 @@ class Stenos:
     def decompress_range(self, frame, bytesoftype: int, csize: int, offset: int, length: int, dst, index_ptr: int | None = None) -> int:
         """One range: bytes [offset, offset + length) of the original array -> dst[:length]."""
         return self.decompress_ranges(frame, bytesoftype, csize, [(offset, length)], [dst], index_ptr)
+
+    def gather_rows(self, frame, bytesoftype: int, csize: int, row_bytes: int, rows, out, index_ptr: int | None = None, dst_stride: int | None = None) -> int:
+        """Row rows[i] of the ORIGINAL array (bytes [r * row_bytes, (r + 1) * row_bytes)) out of frame[:csize] into
+        out[i * dst_stride : i * dst_stride + row_bytes], for every i, in one call.  rows: a contiguous int64 or uint64 CUDA tensor
+        (it stays on the device and may have been written by earlier work on the current stream; a negative int64 is a huge
+        unsigned value and therefore an invalid row).  out: a uint8 CUDA tensor or a raw device address.  dst_stride defaults to
+        row_bytes.  index_ptr: as for decompress_ranges.  Returns the bytes delivered; an invalid row raises
+        STENOS_ERROR_INVALID_PARAMETER with its slot untouched."""
+        import torch
+
+        if not rows.is_cuda or rows.dtype not in (torch.int64, torch.uint64) or not rows.is_contiguous():
+            raise ValueError("rows must be a contiguous int64 or uint64 CUDA tensor")
+        stride = row_bytes if dst_stride is None else dst_stride
+        dst = out if isinstance(out, int) else out.data_ptr()
+        return self._check(self.lib.stenos_hip_gather_rows(self.ctx, frame.data_ptr(), bytesoftype, csize, row_bytes, rows.numel(), rows.data_ptr(), dst, stride, index_ptr,
+                                                           self._stream_ptr()))

@@ -453,6 +453,21 @@ size_t stenos_hip_decompress_ranges(stenos_context* ctx, const void* d_src, size
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return decompress_ranges(ctx, d_src, bytesoftype, bytes, n, offsets, lengths, d_dsts, d_index, (hipStream_t)stream);
 }
+size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n, const uint64_t* d_rows,
+			      void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream)
+{
+	if (n == 0)
+		return 0;
+	if (!ctx || !d_src || !d_rows || !d_dst)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: the shape of the call (n * row_bytes and the end of the last slot must be representable)
+	if (row_bytes == 0 || dst_stride < row_bytes || bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || n > ~(size_t)0 / row_bytes ||
+	    n - 1 > (~(size_t)0 - row_bytes) / dst_stride)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return gather_rows(ctx, d_src, bytesoftype, bytes, row_bytes, n, d_rows, d_dst, dst_stride, d_index, (hipStream_t)stream);
+}
 size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t n, const size_t* bytes)
 {
 	if (bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || (n && !bytes))

@@ -1,0 +1,118 @@
+// range_host_codes.h -- internal to the host side: finishing pieces of superblocks that went through zstd (codes 2-5) one by
+// one, for the calls that deliver parts of a frame (range_host.cpp, gather_host.cpp).  A piece is a RangeUnit {superblock,
+// lo, hi, dst}; the superblock is fetched and inflated on the host, then the piece is copied out (code 2), cut out of the
+// superblock as the byte kernels rebuild it (codes 3, 4), or decoded by a one-unit launch of decode_ranges over the inflated
+// block stream (code 5).  Consecutive pieces of one superblock share the fetch and the inflation.  Slow.
+#pragma once
+#include "host.h"
+#include "range.h"
+
+namespace stenos_host {
+
+inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+
+struct HostCodes {
+	stenos_context_s* ctx;
+	const uint8_t* d_frame;
+	size_t size, T;
+	const uint64_t* d_index;
+	FrameInfo fi;
+	hipStream_t stream;
+	uint8_t* h_tab; // mirror of rtab
+	uint8_t* d_tab;
+	size_t o_one;   // the words and the unit of a one-unit launch (code 5), in both
+	// the superblock the buffers hold: inflated bytes at h_stage + 16 (codes 2 and 5), decoded bytes in rsb (codes 3 and 4)
+	uint64_t have_sb = ~0ull;
+	unsigned have_code = 0;
+	size_t have_bytes = 0;
+
+	bool copy(void* to, const void* from, size_t n, hipMemcpyKind kind) const
+	{
+		return hipMemcpyAsync(to, from, n, kind, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+	}
+	// fetch and inflate superblock s; 0 or an error code
+	size_t load(uint64_t s)
+	{
+		if (s == have_sb)
+			return 0;
+		have_sb = ~0ull;
+		const size_t dsize = superblock_bytes(fi.total, fi.sb, s);
+		uint64_t p = 0;
+		uint8_t hd[4];
+		if (!copy(&p, d_index + s, 8, hipMemcpyDeviceToHost))
+			return STENOS_ERROR_UNDEFINED;
+		if (p > size || size - p < 4)
+			return STENOS_ERROR_SRC_OVERFLOW;
+		if (!copy(hd, d_frame + p, 4, hipMemcpyDeviceToHost))
+			return STENOS_ERROR_UNDEFINED;
+		const unsigned code = hd[0];
+		const size_t csize = (size_t)get_le(hd + 1, 3);
+		if (code < 2 || code > 5 || size - p - 4 < csize)
+			return STENOS_ERROR_INVALID_INPUT;
+		if (!ctx->h_in.ensure(csize + 64) || !ctx->h_stage.ensure(fi.sb + 64 + 32) || !ctx->tmp1.ensure(fi.sb + 64 + 32) || !ctx->tmp2.ensure(fi.sb + 64) ||
+		    !ctx->rsb.ensure(fi.sb + 64))
+			return STENOS_ERROR_ALLOC;
+		if (csize && !copy(ctx->h_in.data(), d_frame + p + 4, csize, hipMemcpyDeviceToHost))
+			return STENOS_ERROR_UNDEFINED;
+		uint8_t* const hs = ctx->h_stage.data();
+		// code 5: zstd over the block stream, at most the superblock size (stenos.cpp:732)
+		const size_t r = zstd().decompress(hs + 16, code == 5 ? fi.sb + 64 : dsize, ctx->h_in.data(), csize);
+		if (zstd().is_error(r) || (code != 5 && code != 2 && r != dsize)) // stenos.cpp:696-698, 706-708, 718-720
+			return STENOS_ERROR_INVALID_INPUT;
+		if (code == 3 || code == 4) { // transposed (stenos.cpp:700-710) / transposed + byte delta (:711-725) -> rsb
+			uint8_t* const t1 = ctx->tmp1.as<uint8_t>();
+			uint8_t* const t2 = ctx->tmp2.as<uint8_t>();
+			bool ok = hipMemcpyAsync(t1, hs + 16, dsize, hipMemcpyHostToDevice, stream) == hipSuccess;
+			if (code == 4)
+				ok = ok && stenos_k_launch_delta(t1, t2, dsize, true, stream) == hipSuccess;
+			ok = ok && stenos_k_launch_shuffle(code == 4 ? t2 : t1, ctx->rsb.as<uint8_t>(), (uint32_t)T, dsize, true, stream) == hipSuccess;
+			if (!ok || hipStreamSynchronize(stream) != hipSuccess)
+				return STENOS_ERROR_UNDEFINED;
+		}
+		else if (code == 5) { // -> one BLOCK superblock for the block decoder (stenos.cpp:726-740), its payload 16-byte aligned
+			write_superblock_header(hs + 12, 1, r);
+			if (!copy(ctx->tmp1.as<uint8_t>() + 12, hs + 12, 4 + r, hipMemcpyHostToDevice))
+				return STENOS_ERROR_UNDEFINED;
+		}
+		have_sb = s;
+		have_code = code;
+		have_bytes = r;
+		return 0;
+	}
+	size_t finish(const RangeUnit& u)
+	{
+		if (size_t e = load(u.sb))
+			return e;
+		const size_t len = u.hi - u.lo;
+		if (have_code == 2) { // plain zstd
+			if (u.hi > have_bytes)
+				return STENOS_ERROR_INVALID_INPUT;
+			return copy(u.dst, ctx->h_stage.data() + 16 + u.lo, len, hipMemcpyHostToDevice) ? 0 : (size_t)STENOS_ERROR_UNDEFINED;
+		}
+		if (have_code != 5)
+			return copy(u.dst, ctx->rsb.as<uint8_t>() + u.lo, len, hipMemcpyDeviceToDevice) ? 0 : (size_t)STENOS_ERROR_UNDEFINED;
+		uint8_t* const h = h_tab + o_one;
+		uint8_t* const d = d_tab + o_one;
+		memset(h, 0, 128);
+		*(RangeUnit*)(h + 64) = u;
+		RangeArgs a = RangeArgs();
+		a.frame = ctx->tmp1.as<uint8_t>();
+		a.size = 16 + have_bytes;
+		a.sb_off = nullptr;
+		a.direct_off = 12;
+		a.units = (const RangeUnit*)(d + 64);
+		a.unit_status = (uint32_t*)(d + 8);
+		a.status = (uint32_t*)d;
+		a.total_bytes = fi.total;
+		a.sb_bytes = (uint32_t)fi.sb;
+		a.T = (uint32_t)T;
+		a.nunits = 1;
+		volatile uint32_t* back = &ctx->h_total->decode_status;
+		if (hipMemcpyAsync(d, h, 128, hipMemcpyHostToDevice, stream) != hipSuccess || stenos_r_launch_decode(a, stream) != hipSuccess ||
+		    !copy((void*)back, d, 4, hipMemcpyDeviceToHost))
+			return STENOS_ERROR_UNDEFINED;
+		return *back ? (size_t)STENOS_ERROR_INVALID_INPUT : 0;
+	}
+};
+
+} // namespace stenos_host
