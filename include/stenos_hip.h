@@ -153,6 +153,79 @@ STENOS_EXPORT size_t stenos_hip_decompress_ranges(stenos_context* ctx, const voi
 STENOS_EXPORT size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n,
 					    const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream);
 
+/* Update: the mirror image of the gather call.  n rows of the ORIGINAL array are replaced, by row numbers that live in DEVICE
+ * memory, and the frame of the updated array is written to a second buffer; the array's size, its superblock size and its
+ * header never change, and the input frame is never modified.  Row r is bytes [r * row_bytes, (r + 1) * row_bytes) of the
+ * array, as in stenos_hip_gather_rows; the row_bytes bytes at d_src + i * src_stride replace row d_rows[i], for i in 0..n.
+ * d_out receives a complete frame; the call returns its size, or an error code for the call as a whole.  d_rows is read on the
+ * device only, and every enqueued step is ordered on `stream`: row numbers and source rows written by earlier work on that
+ * stream need no synchronisation by the caller.  row_bytes >= 1 may be any value (not a multiple of bytesoftype, larger than
+ * a superblock), src_stride >= row_bytes, d_src and d_out may have any alignment.  Bytes of the array behind the last whole
+ * row cannot be addressed and stay as they are.  d_out must overlap neither d_frame nor the source rows.  Waits for completion
+ * (there is no _async form).  n == 0 gives a byte copy of the frame, after the header and index checks below.
+ * THE OUTPUT FRAME is the frame stenos_hip_compress produces for the updated array at the frame's own geometry (the shift or
+ * custom superblock size of its header, not ctx's block-size setting) and ctx's level into a destination of
+ * stenos_bound(array size) bytes: superblocks no row touches are the input's bytes as they are, the touched ones are decoded,
+ * overlaid and encoded again at ctx's level, each on its own -- so if the input frame was made by stenos_hip_compress at that
+ * level into a destination of the bound's size, the whole output is byte-identical to compressing the updated array.  If it
+ * does not fit in out_size the call returns STENOS_ERROR_DST_OVERFLOW (the reference's behaviour for tight destinations is not
+ * imitated).
+ * WRITES TO d_out: on success nothing outside [d_out, d_out + returned size).  Nothing at all on a host-side refusal, an
+ * invalid row number, STENOS_ERROR_DST_OVERFLOW, a refused index or a decode error of a touched superblock: every byte of d_out
+ * is written by the last kernel (update_splice), which is launched only after the status and the new size have come back.
+ * REPEATED ROW NUMBERS: each piece of such a row (a row is cut at superblock boundaries) ends up holding the bytes of one of
+ * its sources, whole; which one is unspecified, and two pieces of one row may hold different sources.
+ * Refused on the host, before any launch, with nothing written:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        row_bytes == 0, src_stride < row_bytes, n * row_bytes or (n - 1) * src_stride +
+ *                                         row_bytes not representable, bytesoftype outside 1..64, more than 2^31 - 1 pieces
+ *                                         (n times the pieces per row of the gather call), while an _async job on ctx is
+ *                                         unfinished, and whatever stenos_hip_compress_batch refuses to compress: ctx's level
+ *                                         >= 2, bytesoftype 1 at level 1, a time limit on ctx;
+ *   a frame header stenos_hip_decompress refuses: its error code.
+ * ROW NUMBERS ARE CHECKED ON THE DEVICE as in the gather call (valid: d_rows[i] < floor(array size / row_bytes)); an invalid
+ * one gives STENOS_ERROR_INVALID_PARAMETER, in front of any decode error.
+ * d_index is as for the gather call: NULL has the chain walked first; an index that is given is used as it is, after a check
+ * that is made before anything is written: offsets must not decrease, every superblock takes at least its 4 header bytes
+ * (and at most what a header can announce), the last entry is at most `bytes` -- else STENOS_ERROR_INVALID_INPUT /
+ * STENOS_ERROR_SRC_OVERFLOW.  No kernel reads outside [d_frame, d_frame + bytes), whatever the index or a size field says.
+ * After a successful call stenos_hip_last_index returns the index of the NEW frame (its superblocks + 1 offsets): the next
+ * gather or update on d_out needs no walk.  A pointer obtained earlier is invalid after the call (after an unsuccessful one
+ * too); an index passed in may be the context's own: it is copied before the context's buffer is written.
+ * HOW: the rows are cut and grouped by superblock on the device (the gather call's kernels); update_plan lists the k
+ * superblocks that hold pieces; update_decode decodes them whole, one wavefront each, into k slots; update_apply copies the
+ * pieces' source bytes in; the slots are encoded as k independent superblocks by the kernels of stenos_hip_compress;
+ * update_splice_plan makes the new index and size; update_splice copies every superblock to its place, one workgroup each.
+ * Host round trips are three -- the header, k with the status, the new size with the status -- and the wait for completion;
+ * launches and round trips depend neither on n nor on the number of superblocks.
+ * DEVICE MEMORY kept by ctx: 40 bytes per superblock of the frame + 16 per piece (tables and both indices); k * superblock
+ * size (the slots); k * (superblock size + 4) + one superblock (their encodings); and the unfused encoder's workspace for k
+ * superblocks -- one padded slot per block of 256 * bytesoftype bytes (about 1.14 x the block for int32), 16 bytes of tables per
+ * block, 37 per superblock: together about 3.2 * k * superblock size.  Proportional to k, never to the array -- but with every
+ * superblock touched that is three times the array.  The buffers never shrink: they stay at the largest size a call needed
+ * until the context is destroyed.
+ * MEASURED on MI355X (profiles/update_rate.txt: 1 GiB int32 frame of 8 192 superblocks, level 1, index passed in, unique uniform
+ * random 4 KiB rows, medians of 20; against stenos_hip_decompress into a scratch tensor + index_copy_ + stenos_hip_compress,
+ * which leave the same frame), update / baseline in microseconds, superblocks touched, device memory held:
+ *        1 row          490 /    785   x1.60      1 superblock     14 MiB against 1030 MiB
+ *      256 rows         538 /    782   x1.45    253 superblocks  116 MiB against 1030 MiB
+ *    4 096 rows       1 015 /    816   x0.80  3 247             1300 MiB
+ *   65 536 rows       2 028 /  1 355   x0.67  8 191             3248 MiB
+ *   every row         2 375 /  3 021   x1.27  8 192             3264 MiB
+ * The whole-frame splice reads and writes the compressed size; decoding and encoding scale with k, and the encode is by the
+ * unfused kernels.  The call wins while the rows touch a small share of the superblocks; scattered rows that touch a third of
+ * them or more while changing little of each are served faster, and with less memory, by stenos_hip_decompress + a write +
+ * stenos_hip_compress; replacing every row is ahead again because the baseline then moves the whole array once more.
+ * WHAT IS CHECKED: touched superblocks are decoded completely; damage in them gives STENOS_ERROR_SRC_OVERFLOW /
+ * STENOS_ERROR_INVALID_INPUT as in stenos_hip_decompress.  Untouched superblocks are copied, not parsed: damage in them is
+ * NOT detected by this call (with d_index == NULL the walk still sees every superblock header) and arrives in d_out.
+ * Touched superblocks with zstd-based codes (the last superblock under 128 bytes of a level-1 frame; every superblock of a
+ * level >= 2 frame, which a level-0/1 context may update) are fetched and inflated on the host, one whole superblock at a
+ * time, which is slow, and encoded again at ctx's level. */
+STENOS_EXPORT size_t stenos_hip_update_rows(stenos_context* ctx, const void* d_frame, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n,
+					    const uint64_t* d_rows, const void* d_src, size_t src_stride, void* d_out, size_t out_size, const uint64_t* d_index,
+					    void* stream);
+
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),
  * byte delta in four quarter streams above 2048 bytes and its inverse.  src and dst must not overlap.

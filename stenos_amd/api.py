@@ -94,6 +94,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_decompress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_decompress_ranges": (sz, [vp, vp, sz, sz, sz, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64), ctypes.POINTER(vp), vp, vp]),
         "stenos_hip_gather_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp]),
+        "stenos_hip_update_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, vp]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
@@ -249,3 +250,21 @@ class Stenos:
         dst = out if isinstance(out, int) else out.data_ptr()
         return self._check(self.lib.stenos_hip_gather_rows(self.ctx, frame.data_ptr(), bytesoftype, csize, row_bytes, rows.numel(), rows.data_ptr(), dst, stride, index_ptr,
                                                            self._stream_ptr()))
+
+    def update_rows(self, frame, bytesoftype: int, csize: int, row_bytes: int, rows, src, out, index_ptr: int | None = None, src_stride: int | None = None) -> int:
+        """The frame of the ORIGINAL array with row rows[i] (bytes [r * row_bytes, (r + 1) * row_bytes)) replaced by
+        src[i * src_stride : i * src_stride + row_bytes], for every i: frame[:csize] -> out, a complete frame, in one call; the input
+        frame is not modified.  rows: as for gather_rows (on the device, ordered on the current stream, as are the source rows).
+        src: a uint8 CUDA tensor or a raw device address; out: a uint8 CUDA tensor that overlaps neither.  src_stride defaults to
+        row_bytes.  index_ptr: as for gather_rows; afterwards last_index() is the index of the new frame.  Returns the new frame's
+        size; an invalid row, a frame that does not fit or damage in a touched superblock raises with `out` untouched.  Where row
+        numbers repeat, each piece of the row holds the bytes of one of its sources."""
+        import torch
+
+        n = 0 if rows is None else rows.numel()
+        if n and (not rows.is_cuda or rows.dtype not in (torch.int64, torch.uint64) or not rows.is_contiguous()):
+            raise ValueError("rows must be a contiguous int64 or uint64 CUDA tensor")
+        stride = row_bytes if src_stride is None else src_stride
+        s = src if isinstance(src, int) or src is None else src.data_ptr()
+        return self._check(self.lib.stenos_hip_update_rows(self.ctx, frame.data_ptr(), bytesoftype, csize, row_bytes, n, rows.data_ptr() if n else None, s, stride,
+                                                           out.data_ptr(), out.numel(), index_ptr, self._stream_ptr()))

@@ -468,6 +468,19 @@ size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t byt
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return gather_rows(ctx, d_src, bytesoftype, bytes, row_bytes, n, d_rows, d_dst, dst_stride, d_index, (hipStream_t)stream);
 }
+size_t stenos_hip_update_rows(stenos_context* ctx, const void* d_frame, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n, const uint64_t* d_rows,
+			      const void* d_src, size_t src_stride, void* d_out, size_t out_size, const uint64_t* d_index, void* stream)
+{
+	if (!ctx || !d_frame || !d_out || (n && (!d_rows || !d_src)))
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: the shape of the call, and what the context could not compress the touched superblocks with
+	if (row_bytes == 0 || src_stride < row_bytes || bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T ||
+	    (n && (n > ~(size_t)0 / row_bytes || n - 1 > (~(size_t)0 - row_bytes) / src_stride)) || needs_strategy(bytesoftype, ctx->level) || ctx->max_nanoseconds)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return update_rows(ctx, d_frame, bytesoftype, bytes, row_bytes, n, d_rows, d_src, src_stride, d_out, out_size, d_index, (hipStream_t)stream);
+}
 size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t n, const size_t* bytes)
 {
 	if (bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || (n && !bytes))
