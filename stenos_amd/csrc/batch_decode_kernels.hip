@@ -109,25 +109,11 @@ hipError_t stenos_b_launch_walk(const DecodeArgs* args, const uint64_t* first, c
 	return hipGetLastError();
 }
 
-template <uint32_t TT>
-static hipError_t launch_decode_batch_t(const DecodeArgs* args, const uint64_t* spre, uint32_t n, uint64_t nsb, uint32_t T, hipStream_t stream)
-{
-	const size_t lds = stenos_k_decode_lds_bytes(T);
-	hipError_t e = hipFuncSetAttribute((const void*)decode_frames_batch<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	if (e != hipSuccess)
-		return e;
-	hipLaunchKernelGGL(decode_frames_batch<TT>, dim3((uint32_t)nsb), dim3(64), lds, stream, (const GlobalDecodeArgs*)args, spre, n);
-	return hipGetLastError();
-}
-
 hipError_t stenos_b_launch_decode(const DecodeArgs* args, const uint64_t* spre, uint32_t n, uint64_t nsb, uint32_t T, hipStream_t stream)
 {
 	if (nsb == 0)
 		return hipSuccess;
-	switch (T) {
-		case 2: return launch_decode_batch_t<2>(args, spre, n, nsb, T, stream);
-		case 4: return launch_decode_batch_t<4>(args, spre, n, nsb, T, stream);
-		case 8: return launch_decode_batch_t<8>(args, spre, n, nsb, T, stream);
-		default: return launch_decode_batch_t<0>(args, spre, n, nsb, T, stream);
-	}
+	return stenos_k_decode_variant(T, [&](auto tt) {
+		return stenos_k_launch_decoder(decode_frames_batch<decltype(tt)::value>, (uint32_t)nsb, T, stream, (const GlobalDecodeArgs*)args, spre, n);
+	});
 }

@@ -1,5 +1,5 @@
 // batch_host.cpp -- many independent items in one pass of kernels (batch.h).
-#include "host.h"
+#include "frame_access.h"
 
 namespace stenos_host {
 
@@ -11,7 +11,6 @@ namespace stenos_host {
 // serially decodes in 214 us, with the parallel walk in 240 us; at 1024 superblocks 428 against 239.  In a batch the serial
 // walks of all items run side by side, while every parallel walk is a launch of its own.
 constexpr uint64_t kBatchSerialWalkMax = 256;
-inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 static size_t batch_refused(stenos_context_s* ctx, size_t T)
 {
@@ -242,10 +241,11 @@ size_t decompress_batch(stenos_context_s* ctx, size_t n, size_t T, const void* c
 	if (hipMemcpyAsync(d + o_args, h + o_args, tab_bytes - o_args, hipMemcpyHostToDevice, stream) != hipSuccess ||
 	    (serial_walks && stenos_b_launch_walk(d_args, (const uint64_t*)(d + o_first), d + o_walk, (uint32_t)n, stream) != hipSuccess))
 		return fail();
-	for (uint32_t i : parallel_walks) // (long chains: the parallel walk of walk.h, one launch per item)
-		if (stenos_k_launch_walk((const uint8_t*)d_srcs[i], src_sizes[i], info[i].header, info[i].nsb, (uint32_t)info[i].sb, (uint64_t*)h_args[i].sb_off, h_args[i].status,
-					 ctx->walk.p, stream) != hipSuccess)
+	for (uint32_t i : parallel_walks) { // (long chains: the parallel walk of walk.h, one launch per item, into the item's part of the index)
+		const uint64_t* none = nullptr;
+		if (frame_offsets(ctx, d_srcs[i], src_sizes[i], info[i], &none, (uint64_t*)h_args[i].sb_off, h_args[i].status, stream))
 			return fail();
+	}
 	if (stenos_b_launch_decode(d_args, (const uint64_t*)(d + o_spre), (uint32_t)n, S, (uint32_t)T, stream) != hipSuccess ||
 	    hipMemcpyAsync(h_status, d + o_status, n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
 		return fail();
@@ -255,10 +255,8 @@ size_t decompress_batch(stenos_context_s* ctx, size_t n, size_t T, const void* c
 		if (is_err(res[i]) || !info[i].total)
 			continue;
 		const uint32_t status = h_status[i];
-		if (status & DECODE_STATUS_TRUNCATED)
-			res[i] = STENOS_ERROR_SRC_OVERFLOW;
-		else if (status & DECODE_STATUS_INVALID)
-			res[i] = STENOS_ERROR_INVALID_INPUT;
+		if (const size_t e = status_error(status))
+			res[i] = e;
 		else if (status & DECODE_STATUS_HOST_CODES) { // zstd-based superblocks: finished on the host, item by item
 			idx.resize(info[i].nsb + 1);
 			if (hipMemcpy(idx.data(), h_args[i].sb_off, (info[i].nsb + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess)

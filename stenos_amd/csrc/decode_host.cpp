@@ -1,7 +1,6 @@
 // decode_host.cpp -- decoding on device memory: frame header checks, the decode launch, the host finish of zstd-coded
 // superblocks, the index of a frame.
-#include <atomic>
-#include "host.h"
+#include "frame_access.h"
 
 namespace stenos_host {
 
@@ -312,31 +311,20 @@ size_t decompress_device(stenos_context_s* ctx, const void* d_src, size_t T, siz
 {
 	if (!ctx->device_ready())
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
-	uint8_t h[12] = { 0 };
-	const size_t have = size < 12 ? size : 12;
-	if (have && (hipMemcpyAsync(h, d_src, have, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess))
-		return STENOS_ERROR_UNDEFINED;
 	FrameInfo fi;
-	size_t e = parse_frame(h, have, T, dst_size, fi);
+	size_t e = fetch_frame_info(d_src, T, size, dst_size, stream, fi);
 	if (is_err(e))
 		return e;
 	ctx->job_kind = 0;
 	if (fi.total == 0)
 		return 0;
-	// (a caller's index may be the context's own, from stenos_hip_last_index / stenos_hip_frame_index: only touch it when none is given)
-	if (!ctx->misc.ensure(4096) || (!d_index && !ctx->sboff.ensure((fi.nsb + 2) * 8)))
+	if (!ctx->misc.ensure(4096))
 		return STENOS_ERROR_ALLOC;
 	uint32_t* d_status = &ctx->words()->decode_status;
 	if (hipMemsetAsync(d_status, 0, 4, stream) != hipSuccess)
 		return STENOS_ERROR_UNDEFINED;
-	if (!d_index) {
-		d_index = ctx->sboff.as<uint64_t>();
-		if (!ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
-			return STENOS_ERROR_ALLOC;
-		if (stenos_k_launch_walk((const uint8_t*)d_src, size, fi.header, fi.nsb, (uint32_t)fi.sb, ctx->sboff.as<uint64_t>(), d_status,
-					 ctx->test_serial_walk ? nullptr : ctx->walk.p, stream) != hipSuccess)
-			return STENOS_ERROR_UNDEFINED;
-	}
+	if ((e = frame_offsets(ctx, d_src, size, fi, &d_index, nullptr, d_status, stream)))
+		return e;
 	DecodeArgs a;
 	if (!decode_args(ctx, d_src, size, d_index, d_dst, fi.total, fi.nsb, fi.sb, T, d_status, a))
 		return STENOS_ERROR_ALLOC;
@@ -370,25 +358,18 @@ const uint64_t* frame_index(stenos_context_s* ctx, const void* d_src, size_t byt
 		*nsb = 0;
 	if (!ctx || !d_src || !ctx->device_ready())
 		return nullptr;
-	uint8_t h[12] = { 0 };
-	const size_t have = bytes < 12 ? bytes : 12;
-	if (have && (hipMemcpyAsync(h, d_src, have, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess))
-		return nullptr;
 	FrameInfo fi;
-	if (is_err(parse_frame(h, have, bytesoftype, ~(size_t)0, fi)) || fi.total == 0)
-		return nullptr;
-	if (!ctx->misc.ensure(4096) || !ctx->sboff.ensure((fi.nsb + 2) * 8) || !ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
+	if (fetch_frame_info(d_src, bytesoftype, bytes, ~(size_t)0, stream, fi) || fi.total == 0 || !ctx->misc.ensure(4096))
 		return nullptr;
 	uint32_t* d_status = &ctx->words()->decode_status;
 	uint32_t status = 0;
-	if (hipMemsetAsync(d_status, 0, 4, stream) != hipSuccess ||
-	    stenos_k_launch_walk((const uint8_t*)d_src, bytes, fi.header, fi.nsb, (uint32_t)fi.sb, ctx->sboff.as<uint64_t>(), d_status,
-				 ctx->test_serial_walk ? nullptr : ctx->walk.p, stream) != hipSuccess ||
+	const uint64_t* index = nullptr;
+	if (hipMemsetAsync(d_status, 0, 4, stream) != hipSuccess || frame_offsets(ctx, d_src, bytes, fi, &index, nullptr, d_status, stream) ||
 	    hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess || status)
 		return nullptr; // a header or payload runs past the end of the frame
 	if (nsb)
 		*nsb = (size_t)fi.nsb;
-	return ctx->sboff.as<uint64_t>();
+	return index;
 }
 
 } // namespace stenos_host

@@ -70,25 +70,9 @@ __global__ __launch_bounds__(64, decode_occupancy(TT)) void decode_superblocks(D
 
 } // namespace
 
-template <uint32_t TT>
-static hipError_t launch_decode_t(const DecodeArgs& a, hipStream_t stream)
-{
-	const size_t lds = stenos_k_decode_lds_bytes(a.T);
-	hipError_t e = hipFuncSetAttribute((const void*)decode_superblocks<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	if (e != hipSuccess)
-		return e;
-	hipLaunchKernelGGL(decode_superblocks<TT>, dim3((uint32_t)a.nsb), dim3(64), lds, stream, a);
-	return hipGetLastError();
-}
-
 hipError_t stenos_k_launch_decode(const DecodeArgs& a, hipStream_t stream)
 {
 	if (a.T > STENOS_K_LDS_MAX_T)
 		return stenos_kw_launch_decode(a, stream);
-	switch (a.T) {
-		case 2: return launch_decode_t<2>(a, stream);
-		case 4: return launch_decode_t<4>(a, stream);
-		case 8: return launch_decode_t<8>(a, stream);
-		default: return launch_decode_t<0>(a, stream);
-	}
+	return stenos_k_decode_variant(a.T, [&](auto tt) { return stenos_k_launch_decoder(decode_superblocks<decltype(tt)::value>, (uint32_t)a.nsb, a.T, stream, a); });
 }

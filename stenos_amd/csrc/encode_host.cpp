@@ -1,6 +1,6 @@
 // encode_host.cpp -- levels 0 and 1 on device memory: frame geometry, the workspace and the FrameJob of the encode
 // pipeline, the kernel sequence of one frame, the device-pointer call and the end of a pending job.
-#include "host.h"
+#include "frame_access.h"
 
 namespace stenos_host {
 
@@ -363,10 +363,8 @@ size_t finish_job(stenos_context_s* ctx)
 		return (estatus || total > ctx->job_dst_size) ? STENOS_ERROR_DST_OVERFLOW : (size_t)total;
 	}
 	const uint32_t status = ctx->h_total->decode_status;
-	if (status & DECODE_STATUS_TRUNCATED)
-		return STENOS_ERROR_SRC_OVERFLOW;
-	if (status & DECODE_STATUS_INVALID)
-		return STENOS_ERROR_INVALID_INPUT;
+	if (const size_t e = status_error(status))
+		return e;
 	ctx->job_host_codes = (status & DECODE_STATUS_HOST_CODES) != 0;
 	return ctx->job_expected;
 }

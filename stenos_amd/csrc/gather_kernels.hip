@@ -178,27 +178,11 @@ hipError_t stenos_g_launch_fill(const GatherArgs& a, hipStream_t stream)
 	return hipGetLastError();
 }
 
-template <uint32_t TT>
-static hipError_t launch_gather_t(const GatherArgs& a, hipStream_t stream)
-{
-	const size_t lds = stenos_k_decode_lds_bytes(a.T);
-	hipError_t e = hipFuncSetAttribute((const void*)gather_decode<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	if (e != hipSuccess)
-		return e;
-	hipLaunchKernelGGL(gather_decode<TT>, dim3(a.waves), dim3(64), lds, stream, a);
-	return hipGetLastError();
-}
-
 hipError_t stenos_g_launch_decode(const GatherArgs& a, hipStream_t stream)
 {
 	if (a.waves == 0)
 		return hipSuccess;
 	if (a.T == 0 || a.T > STENOS_K_LDS_MAX_T)
 		return hipErrorInvalidValue;
-	switch (a.T) {
-		case 2: return launch_gather_t<2>(a, stream);
-		case 4: return launch_gather_t<4>(a, stream);
-		case 8: return launch_gather_t<8>(a, stream);
-		default: return launch_gather_t<0>(a, stream);
-	}
+	return stenos_k_decode_variant(a.T, [&](auto tt) { return stenos_k_launch_decoder(gather_decode<decltype(tt)::value>, a.waves, a.T, stream, a); });
 }

@@ -1,7 +1,8 @@
 // host.h -- internal to the host side of libstenos.so (never installed): the types the units share, the framing helpers
 // and the prototypes they call across.  One unit per concern: host_support.cpp (zstd loader, worker threads),
 // encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, update_host.cpp, host_pointer.cpp and
-// capi.cpp (the exported functions).  Everything here is hidden from the library's users (libstenos.map).
+// capi.cpp (the exported functions); frame_access.h is the front end of those that read a frame in device memory.  Everything here
+// is hidden from the library's users (libstenos.map).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "pipeline.h" // FrameJob (plain pointers and sizes)
 
 enum : uint32_t {
@@ -45,6 +47,31 @@ hipError_t stenos_k_launch_walk(const uint8_t* frame, uint64_t size, uint64_t fi
 				hipStream_t stream);
 size_t stenos_k_walk_scratch_bytes();
 hipError_t stenos_k_launch_decode(const DecodeArgs& a, hipStream_t stream);
+
+// The decode kernels (decode_kernels.hip and the batch, range, gather and update units) are templates over the bytesoftype they
+// are compiled for, TT = 2, 4, 8, or 0 for every other one, which they then read from their arguments.
+// f(std::integral_constant<uint32_t, TT>()) for the TT of bytesoftype T
+template <class F>
+inline hipError_t stenos_k_decode_variant(uint32_t T, F&& f)
+{
+	switch (T) {
+		case 2: return f(std::integral_constant<uint32_t, 2>());
+		case 4: return f(std::integral_constant<uint32_t, 4>());
+		case 8: return f(std::integral_constant<uint32_t, 8>());
+		default: return f(std::integral_constant<uint32_t, 0>());
+	}
+}
+// `grid` workgroups of one wavefront of such a kernel, with the decoder's LDS for bytesoftype T
+template <class K, class... Args>
+inline hipError_t stenos_k_launch_decoder(K kernel, uint32_t grid, uint32_t T, hipStream_t stream, Args... args)
+{
+	const size_t lds = stenos_k_decode_lds_bytes(T);
+	hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	if (e != hipSuccess)
+		return e;
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, stream, args...);
+	return hipGetLastError();
+}
 
 // kernels_wide.hip: bytesoftype above codec::MAX_T of the LDS-resident kernels (the launchers above forward to these)
 constexpr uint32_t STENOS_K_LDS_MAX_T = 64;

@@ -83,27 +83,11 @@ __global__ __launch_bounds__(64, decode_ranges_occupancy(TT)) void decode_ranges
 
 } // namespace
 
-template <uint32_t TT>
-static hipError_t launch_ranges_t(const RangeArgs& a, hipStream_t stream)
-{
-	const size_t lds = stenos_k_decode_lds_bytes(a.T);
-	hipError_t e = hipFuncSetAttribute((const void*)decode_ranges<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	if (e != hipSuccess)
-		return e;
-	hipLaunchKernelGGL(decode_ranges<TT>, dim3(a.nunits), dim3(64), lds, stream, a);
-	return hipGetLastError();
-}
-
 hipError_t stenos_r_launch_decode(const RangeArgs& a, hipStream_t stream)
 {
 	if (a.nunits == 0)
 		return hipSuccess;
 	if (a.T == 0 || a.T > STENOS_K_LDS_MAX_T)
 		return hipErrorInvalidValue;
-	switch (a.T) {
-		case 2: return launch_ranges_t<2>(a, stream);
-		case 4: return launch_ranges_t<4>(a, stream);
-		case 8: return launch_ranges_t<8>(a, stream);
-		default: return launch_ranges_t<0>(a, stream);
-	}
+	return stenos_k_decode_variant(a.T, [&](auto tt) { return stenos_k_launch_decoder(decode_ranges<decltype(tt)::value>, a.nunits, a.T, stream, a); });
 }

@@ -1,6 +1,4 @@
 // range_host.cpp -- byte ranges of one frame in device memory (stenos_hip_decompress_ranges, range.h).
-#include "host.h"
-#include "range.h"
 #include "range_host_codes.h"
 
 namespace stenos_host {
@@ -8,21 +6,16 @@ namespace stenos_host {
 // Every range is cut at the superblock boundaries of the frame; a unit {superblock, lo, hi, dst} is what one wavefront of
 // decode_ranges delivers.  The unit table goes up in one copy from the page-locked mirror h_rtab, in front of it the call's
 // status word (zero); one word comes back.  Launches and host round trips do not grow with the number of ranges: the header
-// fetch, the walk when no index is given, the table, the decode launch, the status.  The table has a buffer of its own
-// (rtab): an index the caller passes may be the context's own (sboff) and stays as it is.
+// fetch, the table, the walk when no index is given, the decode launch, the status (frame_access.h).  The table has a buffer of
+// its own (rtab).
 // Units in superblocks that went through zstd (codes 2-5) come back flagged and are finished here one by one, which is slow.
 size_t decompress_ranges(stenos_context_s* ctx, const void* d_src, size_t T, size_t size, size_t n, const uint64_t* offsets, const uint64_t* lengths,
 			 void* const* d_dsts, const uint64_t* d_index, hipStream_t stream)
 {
 	if (T == 0 || T > STENOS_K_LDS_MAX_T || (ctx->job_kind && ctx->job_async))
 		return STENOS_ERROR_INVALID_PARAMETER;
-	uint8_t head[12] = { 0 };
-	const size_t have = size < 12 ? size : 12;
-	if (have && (hipMemcpyAsync(head, d_src, have, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess))
-		return STENOS_ERROR_UNDEFINED;
 	FrameInfo fi;
-	const size_t e = parse_frame(head, have, T, ~(size_t)0, fi);
-	if (is_err(e))
+	if (const size_t e = fetch_frame_info(d_src, T, size, ~(size_t)0, stream, fi))
 		return e;
 	uint64_t sum = 0, nunits = 0;
 	for (size_t i = 0; i < n; ++i) {
@@ -62,21 +55,15 @@ size_t decompress_ranges(stenos_context_s* ctx, const void* d_src, size_t T, siz
 			at = stop;
 		}
 	}
-	auto fail = [&]() -> size_t {
+	auto fail = [&](size_t code = STENOS_ERROR_UNDEFINED) -> size_t {
 		(void)hipStreamSynchronize(stream);
-		return STENOS_ERROR_UNDEFINED;
+		return code;
 	};
 	uint32_t* const d_status = (uint32_t*)d;
 	if (hipMemcpyAsync(d, h, o_status, hipMemcpyHostToDevice, stream) != hipSuccess)
 		return fail();
-	if (!d_index) { // the chain is walked first, into the context's index
-		if (!ctx->sboff.ensure((fi.nsb + 2) * 8) || !ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
-			return (void)hipStreamSynchronize(stream), STENOS_ERROR_ALLOC;
-		d_index = ctx->sboff.as<uint64_t>();
-		if (stenos_k_launch_walk((const uint8_t*)d_src, size, fi.header, fi.nsb, (uint32_t)fi.sb, ctx->sboff.as<uint64_t>(), d_status,
-					 ctx->test_serial_walk ? nullptr : ctx->walk.p, stream) != hipSuccess)
-			return fail();
-	}
+	if (const size_t e = frame_offsets(ctx, d_src, size, fi, &d_index, nullptr, d_status, stream))
+		return fail(e);
 	RangeArgs a = RangeArgs();
 	a.frame = (const uint8_t*)d_src;
 	a.size = size;
@@ -94,27 +81,15 @@ size_t decompress_ranges(stenos_context_s* ctx, const void* d_src, size_t T, siz
 		return fail();
 	ctx->warm = true;
 	const uint32_t status = *back;
-	if (status & DECODE_STATUS_TRUNCATED)
-		return STENOS_ERROR_SRC_OVERFLOW;
-	if (status & DECODE_STATUS_INVALID)
-		return STENOS_ERROR_INVALID_INPUT;
+	if (const size_t e = status_error(status))
+		return e;
 	if (status & DECODE_STATUS_HOST_CODES) {
 		if (!zstd().ok)
 			return STENOS_ERROR_ZSTD_INTERNAL;
 		uint32_t* const h_status = (uint32_t*)(h + o_status);
 		if (hipMemcpyAsync(h_status, d + o_status, nunits * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
 			return fail();
-		HostCodes hc;
-		hc.ctx = ctx;
-		hc.d_frame = (const uint8_t*)d_src;
-		hc.size = size;
-		hc.T = T;
-		hc.d_index = d_index;
-		hc.fi = fi;
-		hc.stream = stream;
-		hc.h_tab = h;
-		hc.d_tab = d;
-		hc.o_one = o_one;
+		HostCodes hc(ctx, d_src, size, T, d_index, fi, stream, o_one);
 		for (uint64_t u = 0; u < nunits; ++u)
 			if (h_status[u] & DECODE_STATUS_HOST_CODES)
 				if (size_t err = hc.finish(units[u]))

@@ -1,15 +1,13 @@
 // range_host_codes.h -- internal to the host side: finishing pieces of superblocks that went through zstd (codes 2-5) one by
-// one, for the calls that deliver parts of a frame (range_host.cpp, gather_host.cpp).  A piece is a RangeUnit {superblock,
+// one, for the calls that deliver parts of a frame (range_host.cpp, gather_host.cpp, update_host.cpp).  A piece is a RangeUnit {superblock,
 // lo, hi, dst}; the superblock is fetched and inflated on the host, then the piece is copied out (code 2), cut out of the
 // superblock as the byte kernels rebuild it (codes 3, 4), or decoded by a one-unit launch of decode_ranges over the inflated
 // block stream (code 5).  Consecutive pieces of one superblock share the fetch and the inflation.  Slow.
 #pragma once
-#include "host.h"
+#include "frame_access.h"
 #include "range.h"
 
 namespace stenos_host {
-
-inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 struct HostCodes {
 	stenos_context_s* ctx;
@@ -18,14 +16,19 @@ struct HostCodes {
 	const uint64_t* d_index;
 	FrameInfo fi;
 	hipStream_t stream;
-	uint8_t* h_tab; // mirror of rtab
-	uint8_t* d_tab;
-	size_t o_one;   // the words and the unit of a one-unit launch (code 5), in both
+	uint8_t* h_tab; // 128 bytes, page-locked: the words and the unit of a one-unit launch (code 5) ...
+	uint8_t* d_tab; // ... and their place on the device
 	// the superblock the buffers hold: inflated bytes at h_stage + 16 (codes 2 and 5), decoded bytes in rsb (codes 3 and 4)
 	uint64_t have_sb = ~0ull;
 	unsigned have_code = 0;
 	size_t have_bytes = 0;
 
+	// the one-unit tables: 128 bytes at o_one of rtab and its mirror, which the caller has made large enough
+	HostCodes(stenos_context_s* c, const void* frame, size_t frame_size, size_t bytesoftype, const uint64_t* index, const FrameInfo& info, hipStream_t s, size_t o_one = 0)
+		: ctx(c), d_frame((const uint8_t*)frame), size(frame_size), T(bytesoftype), d_index(index), fi(info), stream(s), h_tab(c->h_rtab.data() + o_one),
+		  d_tab(c->rtab.as<uint8_t>() + o_one)
+	{
+	}
 	bool copy(void* to, const void* from, size_t n, hipMemcpyKind kind) const
 	{
 		return hipMemcpyAsync(to, from, n, kind, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
@@ -91,8 +94,8 @@ struct HostCodes {
 		}
 		if (have_code != 5)
 			return copy(u.dst, ctx->rsb.as<uint8_t>() + u.lo, len, hipMemcpyDeviceToDevice) ? 0 : (size_t)STENOS_ERROR_UNDEFINED;
-		uint8_t* const h = h_tab + o_one;
-		uint8_t* const d = d_tab + o_one;
+		uint8_t* const h = h_tab;
+		uint8_t* const d = d_tab;
 		memset(h, 0, 128);
 		*(RangeUnit*)(h + 64) = u;
 		RangeArgs a = RangeArgs();

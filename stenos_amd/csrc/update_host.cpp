@@ -1,15 +1,14 @@
 // update_host.cpp -- rows of one frame in device memory replaced by row numbers that live on the device, the updated frame
 // written to a second buffer (stenos_hip_update_rows, update.h).
-#include "host.h"
-#include "update.h"
 #include "range_host_codes.h"
+#include "update.h"
 
 namespace stenos_host {
 
 // The host knows the shape of the call and, after the first round trip, how many superblocks the rows touch (k); it never reads
-// the row numbers.  On `stream`, in this order:
+// the row numbers.  On `stream`, in this order (the front end: frame_access.h):
 //   the header fetch                                                                     (round trip 1)
-//   the old index into the update's own buffer (a copy of d_index, or the walk), one memset (words, counts, flags, prefixes),
+//   one memset (words, counts, flags, prefixes), the old index into the update's own buffer (a copy of d_index, or the walk),
 //   gather_count, gather_scan, gather_fill (gather.h: the pieces by superblock), update_plan, the words back   (round trip 2)
 //   update_decode, [zstd-based codes of touched superblocks: HostCodes, one whole superblock each], update_apply,
 //   enqueue_compress of the k slots as k superblocks without a frame header, update_splice_plan, the words back (round trip 3)
@@ -17,8 +16,8 @@ namespace stenos_host {
 // Launches and round trips depend neither on n nor on the number of superblocks.  The index is copied first because a
 // caller's index may be the context's own (sboff), which the encoder writes the k offsets of its stream into.
 // Device memory, kept by the context between calls:
-//   utab  64 + 16 nsb (counts, flags, slot, touched) + 8 (nsb + 1) (two prefix tables) + 16 (nsb + 1) (old and new index)
-//         + 16 * pieces, each part rounded up to 64 bytes
+//   utab  the PiecePlan's tables (64 + 8 nsb + 8 (nsb + 1) + 16 * pieces) + 8 nsb (slot, touched) + 16 (nsb + 1) (old and new
+//         index), each part rounded up to 64 bytes
 //   uraw  k * sb                                       the touched superblocks, decoded
 //   uenc  k * (sb + 4) + one superblock's worst case   their encodings
 // and the encoder's workspace for k superblocks (ensure_workspace, slots): proportional to k, never to the array.
@@ -26,32 +25,22 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 		   size_t src_stride, void* d_out, size_t out_size, const uint64_t* d_index, hipStream_t stream)
 {
 	const int level = ctx->level;
-	if (T == 0 || T > STENOS_K_LDS_MAX_T || row_bytes == 0 || src_stride < row_bytes || (ctx->job_kind && ctx->job_async))
-		return STENOS_ERROR_INVALID_PARAMETER;
-	if (n && (n > ~(size_t)0 / row_bytes || n - 1 > (~(size_t)0 - row_bytes) / src_stride)) // n * row_bytes, (n - 1) * src_stride + row_bytes
+	if (T == 0 || T > STENOS_K_LDS_MAX_T || !PiecePlan::shape_ok(row_bytes, n, src_stride) || (ctx->job_kind && ctx->job_async))
 		return STENOS_ERROR_INVALID_PARAMETER;
 	if (needs_strategy(T, level) || level < 0 || ctx->max_nanoseconds) // what stenos_hip_compress_batch refuses to compress
 		return STENOS_ERROR_INVALID_PARAMETER;
-	uint8_t head[12] = { 0 };
-	const size_t have = size < 12 ? size : 12;
-	if (have && (hipMemcpyAsync(head, d_frame, have, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess))
-		return STENOS_ERROR_UNDEFINED;
 	FrameInfo fi;
-	const size_t e = parse_frame(head, have, T, ~(size_t)0, fi);
-	if (is_err(e))
+	if (const size_t e = fetch_frame_info(d_frame, T, size, ~(size_t)0, stream, fi))
 		return e;
 	if (fi.total == 0 && n) // an array without rows: every row number is invalid
 		return STENOS_ERROR_INVALID_PARAMETER;
-	const uint64_t P = fi.total ? codec::gather_pieces_per_row(row_bytes, fi.sb) : 1;
-	if (P > 0x7FFFFFFFull || (uint64_t)n > 0x7FFFFFFFull / P) // one thread per piece, 32-bit places in the piece table
+	PiecePlan plan;
+	if (!plan.init(fi, row_bytes, n))
 		return STENOS_ERROR_INVALID_PARAMETER;
-	const uint64_t npieces = (uint64_t)n * P;
 	ctx->job_kind = 0;
-	// utab: [words, 64 bytes][count: nsb][flags: nsb][ppre: nsb + 1][wpre: nsb + 1] cleared by one memset,
-	//       [slot: nsb][touched: nsb][old index: nsb + 1][new index: nsb + 1][pieces]
-	const size_t o_count = 64, o_flags = o_count + align64(fi.nsb * 4), o_ppre = o_flags + align64(fi.nsb * 4), o_wpre = o_ppre + align64((fi.nsb + 1) * 4),
-		     o_slot = o_wpre + align64((fi.nsb + 1) * 4), o_touched = o_slot + align64(fi.nsb * 4), o_idx = o_touched + align64(fi.nsb * 4),
-		     o_new = o_idx + align64((fi.nsb + 1) * 8), o_pieces = o_new + align64((fi.nsb + 1) * 8), tab_bytes = o_pieces + npieces * sizeof(codec::GatherPiece);
+	// utab: the plan's tables, cleared by one memset up to the pieces, then [slot: nsb][touched: nsb][old index: nsb + 1][new index: nsb + 1]
+	const size_t o_slot = plan.end, o_touched = o_slot + align64(fi.nsb * 4), o_idx = o_touched + align64(fi.nsb * 4), o_new = o_idx + align64((fi.nsb + 1) * 8),
+		     tab_bytes = o_new + align64((fi.nsb + 1) * 8);
 	if (!ctx->utab.ensure(tab_bytes))
 		return STENOS_ERROR_ALLOC;
 	uint8_t* const d = ctx->utab.as<uint8_t>();
@@ -62,20 +51,15 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 		(void)hipStreamSynchronize(stream);
 		return code;
 	};
-	if (hipMemsetAsync(d, 0, o_slot, stream) != hipSuccess)
+	if (hipMemsetAsync(d, 0, plan.o_pieces, stream) != hipSuccess)
 		return fail();
 	if (fi.nsb) {
 		if (d_index) {
 			if (hipMemcpyAsync(d_idx, d_index, (fi.nsb + 1) * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess)
 				return fail();
 		}
-		else {
-			if (!ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
-				return fail(STENOS_ERROR_ALLOC);
-			if (stenos_k_launch_walk((const uint8_t*)d_frame, size, fi.header, fi.nsb, (uint32_t)fi.sb, d_idx, d_words + UPDATE_W_STATUS,
-						 ctx->test_serial_walk ? nullptr : ctx->walk.p, stream) != hipSuccess)
-				return fail();
-		}
+		else if (const size_t e = frame_offsets(ctx, d_frame, size, fi, &d_index, d_idx, d_words + UPDATE_W_STATUS, stream))
+			return fail(e);
 	}
 	// the context's index takes the new frame's at the end, and the encoder's offsets in between: if it has to grow, the copy
 	// above (whose source it may be) is waited for first
@@ -98,51 +82,25 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 	a.T = (uint32_t)T;
 	a.header = (uint32_t)fi.header;
 	a.words = d_words;
-	a.ppre = (const uint32_t*)(d + o_ppre);
+	a.ppre = (const uint32_t*)(d + plan.o_ppre);
 	a.slot = (uint32_t*)(d + o_slot);
 	a.touched = (uint32_t*)(d + o_touched);
-	a.flags = (uint32_t*)(d + o_flags);
-	a.pieces = (const codec::GatherPiece*)(d + o_pieces);
+	a.flags = (uint32_t*)(d + plan.o_flags);
+	a.pieces = (const codec::GatherPiece*)(d + plan.o_pieces);
 	volatile uint32_t* back = &ctx->h_total->decode_status; // (page-locked; 24 bytes from here on are the status words' of the decode paths)
 	static_assert(offsetof(PinnedWords, decode_status) + 24 <= 64, "h_total");
 	uint64_t new_total = fi.header;
 	if (fi.nsb) {
-		if (npieces) {
-			GatherArgs g = GatherArgs();
-			g.frame = a.frame;
-			g.size = size;
-			g.sb_off = d_idx;
-			g.rows = d_rows;
-			g.n = n;
-			g.valid_rows = codec::gather_valid_rows(fi.total, row_bytes);
-			g.npieces = npieces;
-			g.shape.row_bytes = row_bytes;
-			g.shape.dst_stride = src_stride; // (a piece's offset counts from the source rows)
-			g.shape.total = fi.total;
-			g.shape.sb = fi.sb;
-			g.P = (uint32_t)P;
-			g.nsb = a.nsb;
-			g.T = a.T;
-			g.status = d_words + UPDATE_W_STATUS;
-			g.count = (uint32_t*)(d + o_count);
-			g.sb_flags = a.flags;
-			g.ppre = (uint32_t*)(d + o_ppre);
-			g.wpre = (uint32_t*)(d + o_wpre);
-			g.pieces = (codec::GatherPiece*)(d + o_pieces);
-			if (stenos_g_launch_count(g, stream) != hipSuccess || stenos_g_launch_scan(g, stream) != hipSuccess || stenos_g_launch_fill(g, stream) != hipSuccess)
-				return fail();
-		}
+		// (a piece's offset counts from the source rows)
+		if (plan.npieces && !PiecePlan::enqueue(plan.args(d, d_frame, size, d_idx, fi, T, row_bytes, n, d_rows, src_stride, d_words + UPDATE_W_STATUS), stream))
+			return fail();
 		if (stenos_u_launch_plan(a, stream) != hipSuccess || hipMemcpyAsync((void*)back, d_words, 12, hipMemcpyDeviceToHost, stream) != hipSuccess ||
 		    hipStreamSynchronize(stream) != hipSuccess)
 			return fail();
 		ctx->warm = true;
 		uint32_t status = back[UPDATE_W_STATUS];
-		if (status & DECODE_STATUS_BAD_ROW)
-			return STENOS_ERROR_INVALID_PARAMETER;
-		if (status & DECODE_STATUS_TRUNCATED)
-			return STENOS_ERROR_SRC_OVERFLOW;
-		if (status & DECODE_STATUS_INVALID)
-			return STENOS_ERROR_INVALID_INPUT;
+		if (const size_t e = status_error(status))
+			return e;
 		const uint64_t k = back[UPDATE_W_K], last = back[UPDATE_W_LAST];
 		size_t enc_cap = 0;
 		if (k) {
@@ -179,17 +137,7 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 				if (hipMemcpyAsync((void*)h_touched, a.touched, k * 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
 				    hipMemcpyAsync((void*)h_flags, a.flags, fi.nsb * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
 					return fail();
-				HostCodes hc;
-				hc.ctx = ctx;
-				hc.d_frame = a.frame;
-				hc.size = size;
-				hc.T = T;
-				hc.d_index = d_idx;
-				hc.fi = fi;
-				hc.stream = stream;
-				hc.h_tab = ctx->h_rtab.data();
-				hc.d_tab = ctx->rtab.as<uint8_t>();
-				hc.o_one = 0;
+				HostCodes hc(ctx, d_frame, size, T, d_idx, fi, stream);
 				for (uint64_t c = 0; c < k; ++c) {
 					const uint32_t s = h_touched[c];
 					if (s >= fi.nsb || !h_flags[s])
@@ -215,10 +163,8 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 		    hipStreamSynchronize(stream) != hipSuccess)
 			return fail();
 		status = back[UPDATE_W_STATUS];
-		if (status & DECODE_STATUS_TRUNCATED)
-			return STENOS_ERROR_SRC_OVERFLOW;
-		if (status & DECODE_STATUS_INVALID)
-			return STENOS_ERROR_INVALID_INPUT;
+		if (const size_t e = status_error(status))
+			return e;
 		if (k && (ctx->h_total->encode_status || ctx->h_total->total > enc_cap)) // (the roomy stream cannot overflow)
 			return STENOS_ERROR_UNDEFINED;
 		new_total = (uint64_t)back[UPDATE_W_TOTAL] | ((uint64_t)back[UPDATE_W_TOTAL + 1] << 32);

@@ -118,29 +118,13 @@ hipError_t stenos_u_launch_plan(const UpdateArgs& a, hipStream_t stream)
 	return hipGetLastError();
 }
 
-template <uint32_t TT>
-static hipError_t launch_update_decode_t(const UpdateArgs& a, hipStream_t stream)
-{
-	const size_t lds = stenos_k_decode_lds_bytes(a.T);
-	hipError_t e = hipFuncSetAttribute((const void*)update_decode<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	if (e != hipSuccess)
-		return e;
-	hipLaunchKernelGGL(update_decode<TT>, dim3(a.k), dim3(64), lds, stream, a);
-	return hipGetLastError();
-}
-
 hipError_t stenos_u_launch_decode(const UpdateArgs& a, hipStream_t stream)
 {
 	if (a.k == 0)
 		return hipSuccess;
 	if (a.T == 0 || a.T > STENOS_K_LDS_MAX_T)
 		return hipErrorInvalidValue;
-	switch (a.T) {
-		case 2: return launch_update_decode_t<2>(a, stream);
-		case 4: return launch_update_decode_t<4>(a, stream);
-		case 8: return launch_update_decode_t<8>(a, stream);
-		default: return launch_update_decode_t<0>(a, stream);
-	}
+	return stenos_k_decode_variant(a.T, [&](auto tt) { return stenos_k_launch_decoder(update_decode<decltype(tt)::value>, a.k, a.T, stream, a); });
 }
 
 hipError_t stenos_u_launch_apply(const UpdateArgs& a, hipStream_t stream)

@@ -586,3 +586,74 @@ def test_repeated_rows(row_bytes):
     finally:
         st.close()
         ref.close()
+
+
+@pytest.mark.parametrize("own_index", [True, False], ids=["context_index", "no_index"])
+def test_every_call_in_turn_on_one_context(own_index):
+    """ranges, gather, update, then gather, ranges and a whole decode of the updated frame, all on one context: with the context's
+    own index (stenos_hip_last_index: the buffer every walk, the update's encoder and the update's new index are written into)
+    passed to each call, and with no index at all.  Every result is the numpy slice of the original or the updated array; the
+    update leaves the old frame as it was."""
+    torch = _cuda()
+    st = Stenos(level=1)
+    try:
+        T, sb = 4, _sb(4)
+        total = 3 * sb + 256 * T + 37 * T + 5  # three superblocks and a partial one
+        nsb = 4
+        data = _mixed_data(T, total, sb, 7)
+        frame, csize = _compress(st, torch, data, T)
+        old = frame[:csize].cpu().numpy()
+        rng = np.random.default_rng(70)
+
+        def index(n_expected=nsb):
+            if not own_index:
+                return None
+            p, n = st.last_index()
+            assert p and n == n_expected
+            return p
+
+        def check_ranges(f, size, full, p):
+            ranges = [(sb - 3, 7), (2 * sb - 100, sb + 200), (5, 300), (3 * sb - 1, total - 3 * sb + 1), (sb // 2, 2 * sb)]
+            dsts = [torch.full((n + 2 * GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda") for _, n in ranges]
+            assert st.decompress_ranges(f, T, size, ranges, [d.data_ptr() + GUARD for d in dsts], p) == sum(n for _, n in ranges)
+            for (lo, n), d in zip(ranges, dsts):
+                got = d.cpu().numpy()
+                assert np.array_equal(got[GUARD:GUARD + n], full[lo:lo + n]), (lo, n)
+                assert (got[:GUARD] == GUARD_BYTE).all() and (got[GUARD + n:] == GUARD_BYTE).all(), (lo, n)
+
+        def check_gather(f, size, full, p):
+            rb = 300
+            assert sb % rb and (2 * sb) % rb
+            rows = [0, sb // rb, 7, 2 * sb // rb, total // rb - 1, sb // rb + 1, 7]  # rows sb // rb and 2 sb // rb straddle two superblocks
+            out = torch.full((len(rows) * rb + GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+            assert st.gather_rows(f, T, size, rb, _rows_tensor(torch, rows), out, p) == len(rows) * rb
+            got = out.cpu().numpy()
+            assert np.array_equal(got[:len(rows) * rb].reshape(-1, rb), np.stack([full[r * rb:(r + 1) * rb] for r in rows]))
+            assert (got[len(rows) * rb:] == GUARD_BYTE).all()
+
+        p = index()
+        check_ranges(frame, csize, data, p)
+        check_gather(frame, csize, data, p)
+        # update: rows in superblocks 0 and 2 (the last row of superblock 0 among them), none in superblock 1 or 3
+        rb = 512
+        rows = [1, 2 * sb // rb + 3, sb // rb - 1, 3 * sb // rb - 2, 40]
+        assert {r * rb // sb for r in rows} == {0, 2} and {((r + 1) * rb - 1) // sb for r in rows} <= {0, 2}
+        src_np, src_rows = _sources(rng, len(rows), rb, rb)
+        updated = _updated(data, rows, rb, src_rows)
+        out = Out(torch, frame.numel())
+        r = st.update_rows(frame, T, csize, rb, _rows_tensor(torch, rows), torch.from_numpy(src_np).cuda(), out.view, p)
+        new = out.frame(r).copy()
+        assert np.array_equal(frame[:csize].cpu().numpy(), old), "the update modified its input frame"
+        lp, ln = st.last_index()
+        assert lp and ln == nsb
+        new_index = _download(torch, lp, nsb + 1)
+        assert new_index[-1] == r and new_index[0] == 8
+        p = index()
+        check_gather(out.view, r, updated, p)
+        check_ranges(out.view, r, updated, p)
+        assert np.array_equal(_decode(st, torch, out.view, T, r, total), updated)
+        assert np.array_equal(out.frame(r), new) and np.array_equal(frame[:csize].cpu().numpy(), old)
+        # and the old frame still decodes to the original array on the same context
+        assert np.array_equal(_decode(st, torch, frame, T, csize, total), data)
+    finally:
+        st.close()
