@@ -380,6 +380,20 @@ def frame_of_payload(payload: bytes, T: int, dsize: int) -> np.ndarray:
     return np.frombuffer(bytes([0]) + dsize.to_bytes(7, "little") + bytes([1]) + len(payload).to_bytes(3, "little") + payload, dtype=np.uint8).copy()
 
 
+def frame_of_payloads(payloads, T: int, sb_bytes: int, total: int):
+    """A frame of BLOCK superblocks (code 1) around given payloads, whatever they hold: [255][total: 7][sb_bytes: 4], then
+    [1][csize: 3][payload] for every payload -> (frame as uint8 array, offsets of the superblock headers and the end), as make_frame"""
+    assert sb_bytes % (256 * T) == 0 and sb_bytes >= 256 * T
+    assert len(payloads) == -(-total // sb_bytes)
+    out = bytearray(bytes([255]) + total.to_bytes(7, "little") + sb_bytes.to_bytes(4, "little"))
+    offs = []
+    for pay in payloads:
+        offs.append(len(out))
+        out += bytes([1]) + len(pay).to_bytes(3, "little") + bytes(pay)
+    offs.append(len(out))
+    return np.frombuffer(bytes(out), dtype=np.uint8).copy(), offs
+
+
 # ---- data that makes every choice reachable ------------------------------------------------------------------------------
 
 PLANE_STYLES = ("const", "small", "straddle", "runs", "slopes", "walk", "noise", "steps", "rowmix", "tiny_delta")

@@ -78,6 +78,21 @@ def oracle_decode(oracle, payload: bytes, T: int, dsize: int):
     return r, out[:dsize]
 
 
+def prefix_bytes(T: int, dsize: int, hi: int) -> int:
+    """what a decoder asked for bytes up to hi (exclusive) of a superblock of dsize bytes must look at: the blocks up to the one
+    that holds byte hi - 1, which is the whole superblock when that byte lies in the tail"""
+    assert 0 < hi <= dsize
+    bs = 256 * T
+    last = (hi - 1) // bs
+    return (last + 1) * bs if last < dsize // bs else dsize
+
+
+def prefix_decode(oracle, payload: bytes, T: int, dsize: int, hi: int):
+    """The verdict and the bytes a partial decoder owes for any window that ends at hi: so_block_decompress decodes the prefix's
+    blocks in order, returns at the first error and never looks at payload behind them -> (result, the prefix's bytes)"""
+    return oracle_decode(oracle, payload, T, prefix_bytes(T, dsize, hi))
+
+
 def paths(T: int):
     """(build, register path, source misalignment)"""
     return [(b, regs, mis) for b in ("dec", "enc") for regs in ((1, 0) if T in (2, 4, 8) else (0,)) for mis in (0, 7)]
@@ -125,8 +140,9 @@ def forms(lib):
 VARIANTS, DATA_STYLE = sg.VARIANTS, sg.DATA_STYLE
 
 
-def streams_for(T: int, seed: int, names=None, blocks=None):
-    """(name, data, payload, choices) for every variant that applies to T"""
+def streams_for(T: int, seed: int, names=None, blocks=None, nbytes=None):
+    """(name, data, payload, choices) for every variant that applies to T; nbytes: the decoded size of every one (default: one or
+    two blocks and a tail of any length)"""
     rng = np.random.default_rng([seed, T])
     for name, ch in VARIANTS.items():
         if names is not None and name not in names:
@@ -135,7 +151,7 @@ def streams_for(T: int, seed: int, names=None, blocks=None):
             continue
         nblocks = blocks if blocks is not None else (2 if T <= 16 else 1)
         tail = int(rng.integers(0, 256 * T))
-        data = sg.make_data(rng, T, nblocks * 256 * T + tail, DATA_STYLE.get(name))
+        data = sg.make_data(rng, T, nblocks * 256 * T + tail if nbytes is None else nbytes, DATA_STYLE.get(name))
         yield name, data, sg.encode_payload(data, T, ch, rng), ch
 
 
@@ -274,18 +290,19 @@ def mutate(rng, payload: bytes) -> bytes:
     return bytes(b) if b else b"\x00"
 
 
-def mutation_bases(oracle, T: int):
-    """(payload, decoded size): oracle-made payloads of the fuzz kinds and writer-made ones"""
+def mutation_bases(oracle, T: int, dsize: int | None = None):
+    """(payload, decoded size): oracle-made payloads of the fuzz kinds and writer-made ones.  dsize: every base decodes to exactly
+    that many bytes (default: about 600 elements, 300 above bytesoftype 16)"""
     rng = np.random.default_rng([5, T])
     bases = []
     n = 600 if T <= 16 else 300
     for k, kind in enumerate(ORACLE_KINDS):
-        data = generate(kind, T, n + 13 * k, 100 + k)
+        data = generate(kind, T, n + 13 * k, 100 + k) if dsize is None else generate(kind, T, -(-dsize // T), 100 + k)[:dsize].copy()
         buf = np.zeros(data.nbytes * 2 + 4096, dtype=np.uint8)
         r = oracle.so_block_compress(np_ptr(data), T, data.nbytes, np_ptr(buf), buf.nbytes)
         assert not has_error(r)
         bases.append((buf[:r].tobytes(), data.nbytes))
-    for name, data, payload, ch in streams_for(T, 3, names=("legal", "oversize", "mix6715", "lz", "packed+6+7", "copy")):
+    for name, data, payload, ch in streams_for(T, 3, names=("legal", "oversize", "mix6715", "lz", "packed+6+7", "copy"), nbytes=dsize):
         bases.append((payload, data.size))
     return bases
 
