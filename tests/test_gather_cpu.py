@@ -135,6 +135,62 @@ def test_cutting_against_the_model(plain, T):
     assert n > 300  # (pieces compared)
 
 
+SB32 = 131072  # the default superblock of 32-bit elements: the geometry of the arrays beyond 4 GiB
+LARGE_TOTALS = [(1 << 31) + a * SB32 + b for a in (-1, 1) for b in (-1, 1)] + [(1 << 32) + 5 * SB32 + 1003, (1 << 40) + 77]
+
+
+@pytest.mark.parametrize("total", LARGE_TOTALS, ids=lambda t: f"total{t:#x}")
+def test_cutting_against_the_model_at_large_values(plain, total):
+    """The same comparison where a 32-bit temporary in gather_cut would show: arrays around 2^31 bytes, beyond 2^32 and 2^40; rows
+    that end just below, start on and straddle every multiple of 2^31 (every multiple of 2^32 is one), and the last valid row; slot
+    numbers and strides whose product passes 2^32 and 2^40.  Python integers are the model: nothing wraps there, and every
+    expected value is asserted to fit the 64 bits (the 32 bits of lo and hi) the structure gives it."""
+    sb, n = SB32, 0
+    out = (c_uint64 * 4)()
+    # (slot i, stride as a function of row_bytes): i * stride below 2^32, just above it, above 2^40, and the products the device
+    # tests form -- three slots 2^31 + 8 apart, 2^20 + 3 slots of 4 KiB
+    slots = [(0, lambda rb: rb), (1, lambda rb: (1 << 32) + rb), (2, lambda rb: (1 << 31) + 8), (3, lambda rb: (1 << 31) + 8),
+             ((1 << 20) + 2, lambda rb: max(rb, 4096)), ((1 << 32) + 1, lambda rb: rb + 67), ((1 << 31) - 1, lambda rb: max(rb, 513)),
+             ((1 << 40) // 4101 + 1, lambda rb: rb + 4101), (5, lambda rb: (1 << 40) + rb)]
+    boundaries = list(range(1 << 31, total + 1, 1 << 31))  # (none for the two totals just below 2^31: their last rows end there)
+    assert len(boundaries) == total >> 31
+    passed32 = passed40 = 0
+    for row_bytes in (1, 7, 4101, sb + 5):
+        P = plain.emul_gather_pieces_per_row(row_bytes, sb)
+        assert P == model_pieces_per_row(row_bytes, sb) == {1: 1, 7: 2, 4101: 2, sb + 5: 3}[row_bytes]
+        nrows = plain.emul_gather_valid_rows(total, row_bytes)
+        assert nrows == total // row_bytes and nrows * row_bytes <= total < (nrows + 1) * row_bytes
+        rows = {0, nrows - 1, nrows - 2}
+        for b in boundaries:
+            rows |= {r for r in ((b - 1) // row_bytes - 1, (b - 1) // row_bytes, b // row_bytes, b // row_bytes + 1) if 0 <= r < nrows}
+        # (the superblock boundaries next to the array's end: the last whole superblock and the partial one)
+        for b in (total // sb * sb, total // sb * sb - sb):
+            rows |= {r for r in ((b - 1) // row_bytes, b // row_bytes) if 0 <= r < nrows}
+        straddles = 0
+        for row in sorted(rows):
+            for i, f in slots:
+                stride = f(row_bytes)
+                covered = 0
+                for j in range(P + 1):
+                    want = model_cut(row_bytes, stride, total, sb, row, i, j)
+                    got = plain.emul_gather_cut(row_bytes, stride, total, sb, row, i, j, out)
+                    assert (tuple(out) if got else None) == want, (row_bytes, total, row, i, stride, j)
+                    if want:
+                        s, lo, hi, dst = want
+                        assert j < P and lo < hi <= min(sb, total - s * sb) and hi < (1 << 32) and s < (1 << 32) and dst < (1 << 64)
+                        assert dst == i * stride + covered
+                        covered += hi - lo
+                        passed32 += dst >= (1 << 32)
+                        passed40 += dst >= (1 << 40)
+                        n += 1
+                assert covered == row_bytes, "the pieces of a row are the row"
+            off = row * row_bytes
+            straddles += any(off < b < off + row_bytes for b in boundaries)
+        # (a valid row straddles the boundary b when b is no multiple of row_bytes and the row that holds b - 1 is whole)
+        assert bool(straddles) == any(b % row_bytes and (b - 1) // row_bytes < nrows for b in boundaries), (row_bytes, total)
+    assert n > 100 and passed32 > 50 and passed40 > 20, (n, passed32, passed40)  # (pieces compared; destinations beyond 2^32 and 2^40)
+
+
 # ---- the decoder -------------------------------------------------------------------------------------------------------
 
 def gather(plain, audit, buf, csize, T, dsize, pieces, mis, dmis):
