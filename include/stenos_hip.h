@@ -153,6 +153,65 @@ STENOS_EXPORT size_t stenos_hip_decompress_ranges(stenos_context* ctx, const voi
 STENOS_EXPORT size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n,
 					    const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream);
 
+/* Gather from MANY frames in one call: n rows, each out of one of m frames in device memory, by (frame number, row number)
+ * pairs that live in DEVICE memory.  d_frames and sizes are HOST arrays of m: the frames' device pointers and their sizes in
+ * bytes.  Slot i, [d_dst + i * dst_stride, + row_bytes), receives row d_rows[i] of the original array of frame d_frame_ids[i];
+ * row r of a frame is bytes [r * row_bytes, (r + 1) * row_bytes) of that frame's array: the semantics of
+ * stenos_hip_gather_rows, row for row.  One bytesoftype and one row_bytes hold for the call; the frames may differ in size and
+ * in superblock size (each frame's own header decides).  row_bytes >= 1 may be any value, d_dst may have any alignment,
+ * dst_stride >= row_bytes; pairs may repeat, in any order, and two entries of d_frames may name the same frame.  The host
+ * never reads d_frame_ids and d_rows on the common path, and every enqueued step is ordered on `stream`.  Returns n *
+ * row_bytes, or an error code for the call as a whole; n == 0 returns 0 before anything is looked at.  Nothing is ever written
+ * outside the n slots, neither on success nor on any error.  Waits for completion (there is no _async form).
+ * Refused on the host, before any launch that writes to d_dst, with nothing written:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        what stenos_hip_gather_rows refuses (row_bytes == 0, dst_stride < row_bytes, n *
+ *                                         row_bytes or (n - 1) * dst_stride + row_bytes not representable, bytesoftype outside
+ *                                         1..64, an unfinished _async job on ctx); m == 0; m, the superblocks of all frames
+ *                                         together, n times the pieces per pair (below) or the decode grid above 2^31 - 1;
+ *   a frame header stenos_hip_decompress refuses: its error code, for the first such frame in the order of d_frames.
+ * UNLIKE stenos_hip_gather_rows, the frame of an EMPTY array is accepted: it has no valid row and does not fail the call by
+ * being listed.
+ * PAIRS ARE CHECKED ON THE DEVICE: a valid pair has d_frame_ids[i] < m and d_rows[i] < floor(array size / row_bytes) of that
+ * frame (the host computes the bounds).  An invalid pair makes no piece -- its slot is not touched -- and the call then returns
+ * STENOS_ERROR_INVALID_PARAMETER, in front of any decode error; what the other slots hold after that return is unspecified.
+ * d_index: NULL has every chain walked first, into the context's own index (chains of up to 256 superblocks all in one launch,
+ * longer ones by the parallel walk, one launch each).  An index that is given is used as it is.  Its layout: frame f's
+ * superblocks + 1 header offsets start at entry f + (superblocks of the frames in front of f) -- what stenos_hip_frames_index
+ * returns.  The call keeps its tables in a buffer of its own and leaves the context's index intact: index once, gather any
+ * number of times.
+ * The superblocks of all frames are numbered through; every pair is cut at its frame's superblock boundaries on the device (P
+ * pieces per pair, the largest of the frames' own counts, see stenos_hip_gather_rows), the pieces are grouped by superblock
+ * there, and one wavefront walks a superblock's chain of blocks once for up to 64 of its pieces.  Launches and host round trips
+ * depend neither on n nor on the number of superblocks, and on m only through the parallel walks above; the host's own work
+ * and the table it uploads are O(m).
+ * WHO IS SERVED BY WHAT (MI355X, int32, level 1, index passed in; tools/gather_batch_rate.py, profiles/gather_batch_rate.txt,
+ * DESIGN.md 14).  Many frames with a few rows each are what this call is for: 65 536 uniform random pairs of 256 B over 4 096
+ * frames of 64 KiB take 0.27 ms, where a loop of stenos_hip_gather_rows over the 4 096 frames takes 478 ms with the pairs already
+ * grouped on the host -- x1759, all of it the single call's fixed cost of about 117 us per frame.  With the pairs inside 16 frames
+ * the loop of 16 calls is still 11.6 times slower, over 8 frames of 128 MiB a loop of 8 calls 3.6 times (1.68 against 0.47 ms).
+ * With m = 1 this call and stenos_hip_gather_rows cost the same (ratio 1.00 and 0.99 on the 1 GiB frame, inside the noise): a
+ * store that fits one large frame loses nothing by staying one and calling stenos_hip_gather_rows, which needs no frame table.
+ * A loop of single calls serves only a caller whose rows are grouped by frame on the host anyway and touch very few frames.
+ * WHAT IS CHECKED: only the superblocks a row touches are read, and of those only the blocks up to the last byte asked
+ * for.  Damage anywhere else in any frame is NOT detected by this call (with d_index == NULL the walks still see every
+ * superblock header).  A truncated or malformed superblock or block that is decoded gives STENOS_ERROR_SRC_OVERFLOW /
+ * STENOS_ERROR_INVALID_INPUT as in stenos_hip_decompress, for the call as a whole (there are no per-frame results); slots may
+ * then be partly written, inside their bounds.
+ * Superblocks with zstd-based codes (see stenos_hip_gather_rows) are finished on the host: the pairs come down, the pieces of
+ * those superblocks are cut again there, grouped by frame and inflated piece by piece, which is slow. */
+STENOS_EXPORT size_t stenos_hip_gather_rows_batch(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes,
+							  size_t row_bytes, size_t n, const uint64_t* d_frame_ids, const uint64_t* d_rows, void* d_dst, size_t dst_stride,
+							  const uint64_t* d_index, void* stream);
+
+/* The index stenos_hip_gather_rows_batch takes, for m frames in device memory (d_frames, sizes: host arrays of m): every chain
+ * is walked on `stream` and a pointer to DEVICE memory is returned, *entries = its length = the superblocks of all frames + m.
+ * Frame f's slice is what stenos_hip_frame_index gives for that frame (the frame of an empty array has one entry, its end).
+ * NULL for a malformed or truncated frame, m == 0, or whatever the gather call refuses about ctx and bytesoftype.  The array is
+ * the context's own index: valid until the next call on ctx that is not a stenos_hip_gather_rows_batch given this pointer. */
+STENOS_EXPORT const uint64_t* stenos_hip_frames_index(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes,
+							      size_t* entries, void* stream);
+
 /* Update: the mirror image of the gather call.  n rows of the ORIGINAL array are replaced, by row numbers that live in DEVICE
  * memory, and the frame of the updated array is written to a second buffer; the array's size, its superblock size and its
  * header never change, and the input frame is never modified.  Row r is bytes [r * row_bytes, (r + 1) * row_bytes) of the

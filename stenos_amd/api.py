@@ -94,6 +94,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_decompress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_decompress_ranges": (sz, [vp, vp, sz, sz, sz, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64), ctypes.POINTER(vp), vp, vp]),
         "stenos_hip_gather_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp]),
+        "stenos_hip_gather_rows_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, sz, vp, vp, vp, sz, vp, vp]),
+        "stenos_hip_frames_index": (vp, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_update_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, vp]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
@@ -250,6 +252,45 @@ class Stenos:
         dst = out if isinstance(out, int) else out.data_ptr()
         return self._check(self.lib.stenos_hip_gather_rows(self.ctx, frame.data_ptr(), bytesoftype, csize, row_bytes, rows.numel(), rows.data_ptr(), dst, stride, index_ptr,
                                                            self._stream_ptr()))
+
+    def frames_index(self, frames, bytesoftype: int, csizes):
+        """The superblock header offsets of all `frames` (frames[f][:csizes[f]]) in one device array, as gather_rows_batch takes
+        them: (device pointer, entries).  Frame f's superblocks + 1 offsets start at entry f + the superblocks of the frames in
+        front of it.  The pointer is the context's own index: valid until the next call on this context that is not a
+        gather_rows_batch given it.  Raises for a malformed or truncated frame."""
+        m = len(frames)
+        if len(csizes) != m:
+            raise ValueError("frames and csizes must have the same length")
+        P, Z = c_void_p * m, c_size_t * m
+        n = c_size_t(0)
+        p = self.lib.stenos_hip_frames_index(self.ctx, m, bytesoftype, P(*[t.data_ptr() for t in frames]), Z(*csizes), ctypes.byref(n), self._stream_ptr())
+        if not p:
+            raise StenosError((1 << 64) - 4)
+        return p, n.value
+
+    def gather_rows_batch(self, frames, bytesoftype: int, csizes, row_bytes: int, frame_ids, rows, out, index_ptr: int | None = None,
+                          dst_stride: int | None = None) -> int:
+        """gather_rows over many frames in one call: row rows[i] of the ORIGINAL array of frames[frame_ids[i]] goes to
+        out[i * dst_stride : i * dst_stride + row_bytes].  frames: a list of uint8 CUDA tensors (frames[f][:csizes[f]], the same
+        tensor may be listed twice); frame_ids, rows: contiguous int64 or uint64 CUDA tensors of the same length, which stay on
+        the device and may have been written by earlier work on the current stream.  index_ptr: the pointer of frames_index (None:
+        every chain is walked first).  Returns the bytes delivered; an invalid pair (a frame number >= len(frames), a row beyond
+        that frame's array) raises STENOS_ERROR_INVALID_PARAMETER with its slot untouched."""
+        import torch
+
+        for t, name in ((frame_ids, "frame_ids"), (rows, "rows")):
+            if not t.is_cuda or t.dtype not in (torch.int64, torch.uint64) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int64 or uint64 CUDA tensor")
+        if frame_ids.numel() != rows.numel():
+            raise ValueError("frame_ids and rows must have the same length")
+        m = len(frames)
+        if len(csizes) != m:
+            raise ValueError("frames and csizes must have the same length")
+        P, Z = c_void_p * m, c_size_t * m
+        stride = row_bytes if dst_stride is None else dst_stride
+        dst = out if isinstance(out, int) else out.data_ptr()
+        return self._check(self.lib.stenos_hip_gather_rows_batch(self.ctx, m, bytesoftype, P(*[t.data_ptr() for t in frames]), Z(*csizes), row_bytes, rows.numel(),
+                                                                 frame_ids.data_ptr(), rows.data_ptr(), dst, stride, index_ptr, self._stream_ptr()))
 
     def update_rows(self, frame, bytesoftype: int, csize: int, row_bytes: int, rows, src, out, index_ptr: int | None = None, src_stride: int | None = None) -> int:
         """The frame of the ORIGINAL array with row rows[i] (bytes [r * row_bytes, (r + 1) * row_bytes)) replaced by

@@ -6,11 +6,7 @@ namespace stenos_host {
 // The item tables go up in one copy from the page-locked mirror h_btab, the per-item results come back in one; the number
 // of launches and host round trips does not grow with the number of items (the tiny last superblocks add one round trip,
 // items that take the parallel walk or carry zstd-coded superblocks add work of their own).
-// Superblocks up to which a decode item's chain is walked by one lane (walk_frames_batch) instead of the parallel walk of walk.h.
-// Measured on MI355X (tools/batch_rate.py --walk, profiles/batch_rate.txt): a single call that walks 256 superblocks of int32
-// serially decodes in 214 us, with the parallel walk in 240 us; at 1024 superblocks 428 against 239.  In a batch the serial
-// walks of all items run side by side, while every parallel walk is a launch of its own.
-constexpr uint64_t kBatchSerialWalkMax = 256;
+// (a decode item's chain is walked by one lane up to kBatchSerialWalkMax superblocks, frame_access.h)
 
 static size_t batch_refused(stenos_context_s* ctx, size_t T)
 {

@@ -468,6 +468,25 @@ size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t byt
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return gather_rows(ctx, d_src, bytesoftype, bytes, row_bytes, n, d_rows, d_dst, dst_stride, d_index, (hipStream_t)stream);
 }
+size_t stenos_hip_gather_rows_batch(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes, size_t row_bytes, size_t n,
+				    const uint64_t* d_frame_ids, const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream)
+{
+	if (n == 0)
+		return 0;
+	if (!ctx || !d_frames || !sizes || !d_frame_ids || !d_rows || !d_dst)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: no frame, more frames than one thread each, the shape of the call (stenos_hip_gather_rows)
+	if (m == 0 || m > 0x7FFFFFFFull || row_bytes == 0 || dst_stride < row_bytes || bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || n > ~(size_t)0 / row_bytes ||
+	    n - 1 > (~(size_t)0 - row_bytes) / dst_stride)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return gather_rows_batch(ctx, m, bytesoftype, d_frames, sizes, row_bytes, n, d_frame_ids, d_rows, d_dst, dst_stride, d_index, (hipStream_t)stream);
+}
+const uint64_t* stenos_hip_frames_index(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes, size_t* entries, void* stream)
+{
+	return frames_index(ctx, m, bytesoftype, d_frames, sizes, entries, (hipStream_t)stream);
+}
 size_t stenos_hip_update_rows(stenos_context* ctx, const void* d_frame, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n, const uint64_t* d_rows,
 			      const void* d_src, size_t src_stride, void* d_out, size_t out_size, const uint64_t* d_index, void* stream)
 {

@@ -64,6 +64,87 @@ GATHER_HD bool gather_cut(const GatherShape& g, uint64_t row, uint64_t i, uint64
 	return true;
 }
 
+// ---- rows of many frames in one call (stenos_hip_gather_rows_batch, gather_batch.h) ----
+// The superblocks of the batch are numbered through: superblock s of frame f is first_f + s, first_f = the superblocks of the
+// frames in front of it.  One entry per frame, made by the host (gather_frame below) and read by every kernel of the call:
+struct GatherFrame {
+	const uint8_t* frame; // device pointer
+	uint64_t size;        // frame bytes
+	uint64_t total;       // bytes of the original array (0: no row is valid)
+	uint64_t valid_rows;  // gather_valid_rows(total, row_bytes)
+	uint64_t sb;          // superblock bytes of the frame (1 for an empty array: never divided by)
+	uint64_t first;       // number of its superblock 0 in the batch
+	uint32_t nsb;
+	uint32_t pieces;      // gather_pieces_per_row(row_bytes, sb) of this frame: at most the call's P (0 for an empty array)
+};
+
+GATHER_HD GatherFrame gather_frame(const uint8_t* frame, uint64_t size, uint64_t total, uint64_t sb, uint64_t nsb, uint64_t first, uint64_t row_bytes)
+{
+	GatherFrame f;
+	f.frame = frame;
+	f.size = size;
+	f.total = total;
+	f.valid_rows = total ? gather_valid_rows(total, row_bytes) : 0;
+	f.sb = total ? sb : 1;
+	f.first = first;
+	f.nsb = (uint32_t)(total ? nsb : 0);
+	f.pieces = (uint32_t)(total ? gather_pieces_per_row(row_bytes, sb) : 0);
+	return f;
+}
+
+enum { GATHER_PAIR_NONE = 0, GATHER_PAIR_PIECE = 1, GATHER_PAIR_INVALID = -1 };
+
+// Piece j (of the call's P) of the pair (frame number fid, row number row) that goes to slot i, cut with that frame's own shape:
+//   GATHER_PAIR_INVALID  fid >= m or row >= the frame's valid rows: the pair makes no piece (the caller flags it, once per pair);
+//   GATHER_PAIR_NONE     j is beyond the frame's own piece count, or the row does not reach that superblock;
+//   GATHER_PAIR_PIECE    *gsb = first_f + superblock, *p as gather_cut leaves it.
+// The frame's entry is read only after fid has passed its test, row * row_bytes is formed only after row has passed its own.
+GATHER_HD int gather_cut_pair(const GatherFrame* frames, uint64_t m, uint64_t row_bytes, uint64_t dst_stride, uint64_t fid, uint64_t row, uint64_t i, uint64_t j,
+			      uint64_t* gsb, GatherPiece* p)
+{
+	if (fid >= m)
+		return GATHER_PAIR_INVALID;
+	const GatherFrame& f = frames[fid];
+	if (row >= f.valid_rows)
+		return GATHER_PAIR_INVALID;
+	if (j >= f.pieces)
+		return GATHER_PAIR_NONE;
+	const GatherShape g = { row_bytes, dst_stride, f.total, f.sb };
+	uint64_t s;
+	if (!gather_cut(g, row, i, j, &s, p))
+		return GATHER_PAIR_NONE;
+	*gsb = f.first + s;
+	return GATHER_PAIR_PIECE;
+}
+
+// The entry of wavefront / superblock x in exclusive prefix sums: pre[k] <= x < pre[k + 1], entries that span nothing are passed
+// over (batch.h, stenos_b_find_item: in a kernel every lane searches for the same x, so the loads are scalar).  pre has n + 1
+// entries and x < pre[n].
+GATHER_HD uint32_t gather_find32(const uint32_t* pre, uint32_t n, uint32_t x)
+{
+	uint32_t lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (pre[mid] <= x)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+GATHER_HD uint32_t gather_find64(const uint64_t* pre, uint32_t n, uint64_t x)
+{
+	uint32_t lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (pre[mid] <= x)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
 } // namespace codec
 #endif
 
