@@ -1,12 +1,14 @@
 // batch_host.cpp -- many independent items in one pass of kernels (batch.h).
-#include "frame_access.h"
+#include "frame_batch.h"
 
 namespace stenos_host {
 
 // The item tables go up in one copy from the page-locked mirror h_btab, the per-item results come back in one; the number
 // of launches and host round trips does not grow with the number of items (the tiny last superblocks add one round trip,
 // items that take the parallel walk or carry zstd-coded superblocks add work of their own).
-// (a decode item's chain is walked by one lane up to kBatchSerialWalkMax superblocks, frame_access.h)
+// decompress_batch gets from the frames' pointers and sizes to a walked index through the front end of the calls that read many
+// frames (FrameBatch, frame_batch.h: the head fetch, the numbering, the choice of walk); the item tables, the per-item status
+// words and what becomes of a refused item are its own.
 
 static size_t batch_refused(stenos_context_s* ctx, size_t T)
 {
@@ -170,7 +172,7 @@ size_t decompress_batch(stenos_context_s* ctx, size_t n, size_t T, const void* c
 	if (n >= 0x7FFFFFFFull)
 		return STENOS_ERROR_INVALID_PARAMETER;
 	ctx->job_kind = 0;
-	// 1. the first bytes of every frame, for the header checks of the single call (parse_frame)
+	// 1. the first bytes of every frame, for the header checks of the single call (FrameBatch::fetch_heads)
 	const size_t o_frames = 0, o_sizes = align64(n * 8), o_heads = o_sizes + align64(n * 8), head_bytes = o_heads + align64(n * 12);
 	// 2. the items' decode arguments, superblock prefix sums, walk start and choice, status words
 	const size_t o_args = head_bytes, o_spre = o_args + align64(n * sizeof(DecodeArgs)), o_first = o_spre + align64((n + 1) * 8), o_walk = o_first + align64(n * 8),
@@ -183,65 +185,31 @@ size_t decompress_batch(stenos_context_s* ctx, size_t n, size_t T, const void* c
 		(void)hipStreamSynchronize(stream);
 		return STENOS_ERROR_UNDEFINED;
 	};
-	for (size_t i = 0; i < n; ++i) {
-		((const void**)(h + o_frames))[i] = d_srcs[i];
-		((uint64_t*)(h + o_sizes))[i] = src_sizes[i];
-	}
-	if (hipMemcpyAsync(d, h, o_heads, hipMemcpyHostToDevice, stream) != hipSuccess ||
-	    stenos_b_launch_heads((const uint8_t* const*)(d + o_frames), (const uint64_t*)(d + o_sizes), (uint32_t)n, d + o_heads, stream) != hipSuccess ||
-	    hipMemcpyAsync(h + o_heads, d + o_heads, n * 12, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-		return fail();
-	std::vector<size_t> res(n, 0);
-	std::vector<FrameInfo> info(n);
-	uint64_t S = 0;
-	for (size_t i = 0; i < n; ++i) {
-		const size_t have = src_sizes[i] < 12 ? src_sizes[i] : 12;
-		const size_t e = parse_frame(h + o_heads + 12 * i, have, T, dst_sizes[i], info[i]);
-		if (is_err(e))
-			res[i] = e;
-		else if (info[i].total)
-			S += info[i].nsb;
-	}
+	FrameBatch b{ ctx, n, d_srcs, src_sizes, stream };
+	if (const size_t e = b.fetch_heads(T, h, d, o_frames, o_sizes, o_heads, dst_sizes))
+		return e;
+	const std::vector<FrameInfo>& info = b.info;
+	std::vector<size_t> res = b.error; // (a refused item keeps its error code; the others go on)
+	b.number();
+	const uint64_t S = b.S;
 	if (S >= 0x7FFFFFFFull)
 		return STENOS_ERROR_INVALID_PARAMETER;
-	ctx->last_nsb = 0; // (the index workspace holds the batch's superblock offsets from here on)
-	ctx->last_batch = true;
-	if (!ctx->sboff.ensure((S + n + 1) * 8) || !ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
-		return STENOS_ERROR_ALLOC;
 	DecodeArgs* h_args = (DecodeArgs*)(h + o_args);
-	uint64_t* h_spre = (uint64_t*)(h + o_spre);
-	uint64_t* h_first = (uint64_t*)(h + o_first);
-	uint8_t* h_walk = h + o_walk;
 	uint32_t* h_status = (uint32_t*)(h + o_status);
 	const DecodeArgs* d_args = (const DecodeArgs*)(d + o_args);
-	std::vector<uint32_t> parallel_walks;
-	bool serial_walks = false;
-	uint64_t s0 = 0;
+	// (an empty array has nothing to decode and no chain to walk)
+	if (const size_t e = b.plan_walks(h_args, (uint64_t*)(h + o_first), h + o_walk, (uint32_t*)(d + o_status), 1, false))
+		return e;
 	for (size_t i = 0; i < n; ++i) {
 		const bool go = !is_err(res[i]) && info[i].total;
-		DecodeArgs a;
-		if (!decode_args(ctx, d_srcs[i], src_sizes[i], ctx->sboff.as<uint64_t>() + s0 + i, d_dsts[i], go ? info[i].total : 0, go ? info[i].nsb : 0, info[i].sb, T,
-				 (uint32_t*)(d + o_status) + i, a))
+		if (!decode_args(ctx, d_srcs[i], src_sizes[i], h_args[i].sb_off, d_dsts[i], go ? info[i].total : 0, b.nsb(i), info[i].sb, T, h_args[i].status, h_args[i]))
 			return STENOS_ERROR_ALLOC;
-		h_args[i] = a;
-		h_spre[i] = s0;
-		h_first[i] = info[i].header;
-		h_walk[i] = go && (a.nsb <= kBatchSerialWalkMax || ctx->test_serial_walk);
 		h_status[i] = 0;
-		serial_walks |= h_walk[i] != 0;
-		if (go && !h_walk[i])
-			parallel_walks.push_back((uint32_t)i);
-		s0 += a.nsb;
 	}
-	h_spre[n] = s0;
+	memcpy(h + o_spre, b.first.data(), (n + 1) * 8);
 	if (hipMemcpyAsync(d + o_args, h + o_args, tab_bytes - o_args, hipMemcpyHostToDevice, stream) != hipSuccess ||
-	    (serial_walks && stenos_b_launch_walk(d_args, (const uint64_t*)(d + o_first), d + o_walk, (uint32_t)n, stream) != hipSuccess))
+	    b.launch_walks(h_args, d_args, (const uint64_t*)(d + o_first), d + o_walk))
 		return fail();
-	for (uint32_t i : parallel_walks) { // (long chains: the parallel walk of walk.h, one launch per item, into the item's part of the index)
-		const uint64_t* none = nullptr;
-		if (frame_offsets(ctx, d_srcs[i], src_sizes[i], info[i], &none, (uint64_t*)h_args[i].sb_off, h_args[i].status, stream))
-			return fail();
-	}
 	if (stenos_b_launch_decode(d_args, (const uint64_t*)(d + o_spre), (uint32_t)n, S, (uint32_t)T, stream) != hipSuccess ||
 	    hipMemcpyAsync(h_status, d + o_status, n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
 		return fail();

@@ -1,6 +1,7 @@
-// frame_access.h -- internal to the host side: the front end the calls that read a frame in device memory share
-// (decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, update_host.cpp).  Each rule once: the header fetch, the
-// index a call works with, the error code of a status word, the piece tables of the calls that take row numbers.
+// frame_access.h -- internal to the host side: the front end the calls that read one frame in device memory share
+// (decode_host.cpp, range_host.cpp, gather_host.cpp, update_host.cpp).  Each rule once: the header fetch, the index a call works
+// with, the error code of a status word, the piece tables of the calls that take row numbers.  The calls that read many frames
+// (batch_host.cpp, gather_batch_host.cpp) have theirs beside it, on top of this one: frame_batch.h.
 #pragma once
 #include "host.h"
 #include "gather.h"
@@ -9,7 +10,8 @@ namespace stenos_host {
 
 inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
-// Superblocks up to which a batch item's chain is walked by one lane (walk_frames_batch) instead of the parallel walk of walk.h.
+// Superblocks up to which a chain of a call over many frames (frame_batch.h) is walked by one lane (walk_frames_batch) instead
+// of the parallel walk of walk.h.
 // Measured on MI355X (tools/batch_rate.py --walk, profiles/batch_rate.txt): a single call that walks 256 superblocks of int32
 // serially decodes in 214 us, with the parallel walk in 240 us; at 1024 superblocks 428 against 239.  In a batch the serial
 // walks of all items run side by side, while every parallel walk is a launch of its own.

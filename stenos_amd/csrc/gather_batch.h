@@ -6,9 +6,10 @@
 //   gather_scan          gather.h's, over the S superblocks of the batch
 //   gather_batch_fill    the same threads: the piece goes to pieces[ppre[g] + count[g]++]
 //   gather_batch_decode  wavefront w finds its superblock g by wpre[g] <= w < wpre[g + 1], the frame by first[f] <= g < first[f + 1]
-//                        and takes up to 64 pieces of it; wavefronts from wpre[S] on leave at once
-// The index is the concatenation decompress_batch uses: frame f's nsb_f + 1 offsets start at entry f + first_f, so the header of
-// superblock g of frame f is entry g + f.
+//                        and takes up to 64 pieces of it, by the rule gather_decode follows (gather_codec.h, decode_gather_chunk);
+//                        wavefronts from wpre[S] on leave at once
+// The numbering and the index are those of every call over many frames (frame_batch.h): frame f's nsb_f + 1 offsets start at entry
+// f + first_f, so the header of superblock g of frame f is entry g + f.
 #pragma once
 #include "gather.h"
 

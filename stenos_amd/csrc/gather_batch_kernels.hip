@@ -1,8 +1,8 @@
 // gather_batch_kernels.hip -- gfx950 kernels behind stenos_hip_gather_rows_batch (gather_batch.h):
 //   gather_batch_count, gather_batch_fill   the pieces of all pairs, ordered by the batch's superblock numbers, on the device
 //                                           (gather_scan of gather_kernels.hip runs between them)
-//   gather_batch_decode  one wavefront per (superblock of the batch, chunk of up to 64 of its pieces), through the functions of
-//                        gather_codec.h that gather_decode uses
+//   gather_batch_decode  one wavefront per (superblock of the batch, chunk of up to 64 of its pieces): decode_gather_chunk of
+//                        gather_codec.h, which gather_decode calls too, on what the frame table says
 // Compiled with the decoder's options (csrc/Makefile, decode_kernels.hip): gather_batch_decode has no divergent branch.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -16,11 +16,6 @@ using namespace wv;
 namespace {
 
 extern __shared__ __attribute__((aligned(16))) uint8_t g_lds[];
-
-constexpr uint32_t PIECE_THREADS = 256;
-
-// Waves per SIMD, by the rule of gather_decode (gather_kernels.hip): the mini-LZ decoder of 32-bit elements spills at eight.
-constexpr uint32_t gather_batch_decode_occupancy(uint32_t TT) { return TT == 4 ? 7 : 8; }
 
 // The piece of thread t = i * P + j; false: none (beyond the table, an invalid pair -- flagged --, a j beyond the frame's own
 // piece count, a row that ends in front).
@@ -64,47 +59,9 @@ struct GlobalGatherFrame {
 static_assert(sizeof(GlobalGatherFrame) == sizeof(GatherFrame) && offsetof(GlobalGatherFrame, nsb) == offsetof(GatherFrame, nsb), "");
 #undef GLOBAL
 
-// DECODE_STATUS_* bits of one chunk (0: its pieces are in place): decode_gather_chunk of gather_kernels.hip with the frame's
-// pointer, size and shape out of the table.  g: the superblock's number in the batch, f: its frame.
+// g: the superblock's number in the batch, f: its frame, whose pointer, size and shape come out of the table
 template <uint32_t TT>
-__device__ __forceinline__ uint32_t decode_gather_batch_chunk(const GatherBatchArgs& a, uint32_t g, uint32_t f, const uint8_t* tab, uint32_t count)
-{
-	const uint32_t T = TT ? TT : a.T;
-	const GlobalGatherFrame& fr = ((const GlobalGatherFrame*)a.frames)[f];
-	const uint8_t* const frame = (const uint8_t*)fr.frame;
-	const uint64_t size = fr.size, total = fr.total, sb = fr.sb;
-	const uint64_t p = a.sb_off[(uint64_t)g + f];
-	if (p > size || size - p < 4) // (written without sums: an index entry may hold anything)
-		return DECODE_STATUS_TRUNCATED;
-	const uint32_t code = frame[p];
-	const uint32_t csize = (uint32_t)frame[p + 1] | ((uint32_t)frame[p + 2] << 8) | ((uint32_t)frame[p + 3] << 16);
-	const uint64_t begin = (g - fr.first) * sb;
-	if (begin >= total) // (the host's table: first[f] <= g < first[f] + nsb_f)
-		return DECODE_STATUS_INVALID;
-	const uint32_t dsize = (uint32_t)((total - begin) < sb ? (total - begin) : sb);
-	if (size - p - 4 < csize) // stenos.cpp:1133-1134
-		return DECODE_STATUS_TRUNCATED;
-	const LanePieces q = load_pieces(tab, count);
-	if (ballot((q.lo > q.hi) | (q.hi > U32(dsize)))) // (gather_batch_fill writes no such piece)
-		return DECODE_STATUS_INVALID;
-	const uint8_t* payload = frame + p + 4;
-	if (code == 1)
-		return decode_superblock_pieces(g_lds, make_dec_layout(T), T, payload, csize, dsize, q, a.dst) == DEC_ERROR ? DECODE_STATUS_INVALID : 0u;
-	if (code == 6) { // stenos.cpp:741-746
-		if (csize != dsize)
-			return DECODE_STATUS_INVALID;
-		copy_superblock_pieces(payload, q, a.dst);
-		return 0;
-	}
-	if (code >= 2 && code <= 5) { // zstd based codes are finished by the host
-		gstore_uniform(a.sb_flags + g, 1u);
-		return DECODE_STATUS_HOST_CODES;
-	}
-	return DECODE_STATUS_INVALID;
-}
-
-template <uint32_t TT>
-__global__ __launch_bounds__(64, gather_batch_decode_occupancy(TT)) void gather_batch_decode(GatherBatchArgs a)
+__global__ __launch_bounds__(64, gather_decode_occupancy(TT)) void gather_batch_decode(GatherBatchArgs a)
 {
 	const uint32_t w = blockIdx.x;
 	if (w >= a.wpre[a.S])
@@ -112,7 +69,9 @@ __global__ __launch_bounds__(64, gather_batch_decode_occupancy(TT)) void gather_
 	const uint32_t g = gather_find32(a.wpre, a.S, w);
 	const uint32_t f = gather_find64(a.first, a.m, g);
 	const uint32_t first = a.ppre[g] + 64u * (w - a.wpre[g]), left = a.ppre[g + 1] - first;
-	const uint32_t st = decode_gather_batch_chunk<TT>(a, g, f, (const uint8_t*)(a.pieces + first), left < 64u ? left : 64u);
+	const GlobalGatherFrame& fr = ((const GlobalGatherFrame*)a.frames)[f];
+	const uint32_t st = decode_gather_chunk<TT>(g_lds, a.T, (const uint8_t*)fr.frame, fr.size, fr.total, fr.sb, g - fr.first, a.sb_off[(uint64_t)g + f],
+						(const uint8_t*)(a.pieces + first), left < 64u ? left : 64u, a.dst, a.sb_flags + g);
 	if (st)
 		status_or(a.status, st);
 }

@@ -1,8 +1,10 @@
-// gather_codec.h -- rows of one frame gathered by row number (stenos_hip_gather_rows, gather.h): how a row is cut into pieces at
-// the frame's superblock boundaries, and how one wavefront delivers up to 64 pieces of one BLOCK superblock (code 1) with
-// one walk over its chain of blocks.  The cutting is plain C++: the kernels (gather_kernels.hip), the host unit
-// (gather_host.cpp, which defines GATHER_CUT_ONLY and gets nothing else) and the host emulation (tests/emul_gather) include
-// the one copy.  The decoder is written in the wavevec.h vocabulary, so the emulation runs the same code.
+// gather_codec.h -- rows gathered by row number out of one frame (stenos_hip_gather_rows, gather.h) or many
+// (stenos_hip_gather_rows_batch, gather_batch.h): how a row is cut into pieces at the frame's superblock boundaries, what a
+// wavefront does with its superblock (decode_gather_chunk: the index entry and the header checked, the dispatch on the code), and
+// how it delivers up to 64 pieces of one BLOCK superblock (code 1) with one walk over its chain of blocks.  The cutting is plain
+// C++: the kernels (gather_kernels.hip, gather_batch_kernels.hip), the host units (which define GATHER_CUT_ONLY and get nothing
+// else) and the host emulations (tests/emul_gather, tests/emul_gather_batch) include the one copy.  The chunk rule and the decoder
+// are written in the wavevec.h vocabulary, so the emulation runs the same code as both kernels.
 // (two include guards: gather.h takes the cutting alone, a kernel file that includes it takes the rest afterwards)
 #ifndef STENOS_GATHER_CUT_H
 #define STENOS_GATHER_CUT_H
@@ -307,6 +309,66 @@ WV_FN void copy_superblock_pieces(const uint8_t* payload, const LanePieces& q, u
 		copy_g2g_wide<COPY_ROUNDS>(piece_target(dst, q, l, plo), payload + plo, readlane(q.hi, l) - plo);
 	}
 }
+
+// ---- what a gather wavefront does with its superblock (gather_decode, gather_batch_decode, tests/emul_gather) ----
+// DECODE_STATUS_* (kernels.h, which the emulation cannot include; gather_kernels.hip asserts that they are the same)
+enum : uint32_t { GATHER_ST_TRUNCATED = 1, GATHER_ST_INVALID = 2, GATHER_ST_HOST_CODES = 4 };
+
+// a byte of the frame, the same for every lane (the emulation's accessor is the audited one)
+#ifdef WV_HOST_EMULATION
+WV_FN uint32_t frame_u8(const uint8_t* p) { return gload_uniform8(p); }
+#else
+WV_FN uint32_t frame_u8(const uint8_t* p) { return *p; }
+#endif
+
+// One chunk: `count` (1..64) entries of the piece table at tab, all of superblock s of the frame (`size` bytes; the array has
+// `total` bytes in superblocks of sb) whose header the index puts at p.  The status bits of the chunk; 0: its pieces are in place
+// at dst + their offsets.  A superblock that went through zstd (codes 2-5) sets *flag and is left to the host.
+// TT: the bytesoftype the caller is compiled for, 0: the one in `bytesoftype` (kernels.h, stenos_k_decode_variant).  (A template
+// for the registers' sake as well: as a plain function, called from all four kernels of a unit, it leaves the one for bytesoftype
+// 8 a spilled vector register.)
+template <uint32_t TT>
+WV_FN uint32_t decode_gather_chunk(Lds lds, uint32_t bytesoftype, const uint8_t* frame, uint64_t size, uint64_t total, uint64_t sb, uint64_t s, uint64_t p,
+				   const uint8_t* tab, uint32_t count, uint8_t* dst, uint32_t* flag)
+{
+	const uint32_t T = TT ? TT : bytesoftype;
+	if (p > size || size - p < 4) // (written without sums: an index entry may hold anything)
+		return GATHER_ST_TRUNCATED;
+	const uint32_t code = frame_u8(frame + p);
+	const uint32_t csize = frame_u8(frame + p + 1) | (frame_u8(frame + p + 2) << 8) | (frame_u8(frame + p + 3) << 16);
+	const uint64_t begin = s * sb;
+	if (begin >= total) // (the host's tables: s is a superblock of the frame)
+		return GATHER_ST_INVALID;
+	const uint32_t dsize = (uint32_t)((total - begin) < sb ? (total - begin) : sb);
+	if (size - p - 4 < csize) // stenos.cpp:1133-1134
+		return GATHER_ST_TRUNCATED;
+	const LanePieces q = load_pieces(tab, count);
+	if (ballot((q.lo > q.hi) | (q.hi > U32(dsize)))) // (the fill kernels write no such piece)
+		return GATHER_ST_INVALID;
+	const uint8_t* payload = frame + p + 4;
+	if (code == 1)
+		return decode_superblock_pieces(lds, make_dec_layout(T), T, payload, csize, dsize, q, dst) == DEC_ERROR ? GATHER_ST_INVALID : 0u;
+	if (code == 6) { // stenos.cpp:741-746
+		if (csize != dsize)
+			return GATHER_ST_INVALID;
+		copy_superblock_pieces(payload, q, dst);
+		return 0;
+	}
+	if (code >= 2 && code <= 5) { // zstd based codes are finished by the host
+		gstore_uniform(flag, 1u);
+		return GATHER_ST_HOST_CODES;
+	}
+	return GATHER_ST_INVALID;
+}
+
+// ---- what the two translation units share besides (each defines its kernels in its own unnamed namespace) ----
+constexpr uint32_t PIECE_THREADS = 256; // of the count and fill kernels: one thread per (row or pair, piece)
+
+// Waves per SIMD gather_decode and gather_batch_decode are compiled for at bytesoftype TT: eight, as decode_superblocks
+// (decode_kernels.hip).  The kernel holds one decoder (the LDS-image path; whole superblocks take it too) and the lane's piece in
+// four registers across it.  Bytesoftype 4 (the mini-LZ decoder of 32-bit elements is the widest) spills eight registers at
+// eight (64 vector registers); at seven it has 72 and spills none.
+constexpr uint32_t gather_decode_occupancy(uint32_t TT) { return TT == 4 ? 7 : 8; }
 
 } // namespace codec
 #endif

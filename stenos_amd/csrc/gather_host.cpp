@@ -1,6 +1,4 @@
 // gather_host.cpp -- rows of one frame in device memory by row numbers that live on the device (stenos_hip_gather_rows, gather.h).
-#include <algorithm>
-
 #include "range_host_codes.h"
 
 namespace stenos_host {
@@ -9,7 +7,8 @@ namespace stenos_host {
 // given, gather_count, gather_scan, gather_fill (the PiecePlan of frame_access.h, in a buffer of the call's own, gtab),
 // gather_decode, the status word back -- so launches and host round trips grow neither with n nor with the frame.
 // Pieces in superblocks that went through zstd (codes 2-5) are rebuilt here from the row numbers, with the kernels' own
-// cutting function, and finished one by one as the ranges call finishes its units (range_host_codes.h), which is slow.
+// cutting function, and finished one by one as the ranges call finishes its units (range_host_codes.h, finish_flagged_pieces),
+// which is slow.
 size_t gather_rows(stenos_context_s* ctx, const void* d_src, size_t T, size_t size, size_t row_bytes, size_t n, const uint64_t* d_rows, void* d_dst,
 		   size_t dst_stride, const uint64_t* d_index, hipStream_t stream)
 {
@@ -50,38 +49,12 @@ size_t gather_rows(stenos_context_s* ctx, const void* d_src, size_t T, size_t si
 	const uint32_t status = *back;
 	if (const size_t e = status_error(status))
 		return e;
-	if (status & DECODE_STATUS_HOST_CODES) {
-		if (!zstd().ok)
-			return STENOS_ERROR_ZSTD_INTERNAL;
-		// the row numbers and the flags come down; the pieces of the flagged superblocks are cut again here
-		const size_t o_hflags = align64(n * 8);
-		if (!ctx->h_gtab.ensure(o_hflags + fi.nsb * 4) || !ctx->rtab.ensure(128) || !ctx->h_rtab.ensure(128))
-			return STENOS_ERROR_ALLOC;
-		const uint64_t* const h_rows = (const uint64_t*)ctx->h_gtab.data();
-		const uint32_t* const h_flags = (const uint32_t*)(ctx->h_gtab.data() + o_hflags);
-		if (hipMemcpyAsync((void*)h_rows, d_rows, n * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-		    hipMemcpyAsync((void*)h_flags, a.sb_flags, fi.nsb * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-			return fail();
-		std::vector<RangeUnit> units;
-		for (uint64_t i = 0; i < n; ++i)
-			for (uint64_t j = 0; j < P; ++j) {
-				uint64_t s;
-				codec::GatherPiece p;
-				if (h_rows[i] >= a.valid_rows || !codec::gather_cut(a.shape, h_rows[i], i, j, &s, &p) || !h_flags[s])
-					continue;
-				RangeUnit u;
-				u.dst = (uint8_t*)d_dst + p.dst;
-				u.sb = (uint32_t)s;
-				u.lo = p.lo;
-				u.hi = p.hi;
-				u.unused = 0;
-				units.push_back(u);
-			}
-		std::stable_sort(units.begin(), units.end(), [](const RangeUnit& x, const RangeUnit& y) { return x.sb < y.sb; });
-		HostCodes hc(ctx, d_src, size, T, d_index, fi, stream);
-		for (const RangeUnit& u : units)
-			if (size_t err = hc.finish(u))
-				return err;
+	if (status & DECODE_STATUS_HOST_CODES) { // (a batch of one frame, numbered from 0)
+		const codec::GatherFrame frame = codec::gather_frame((const uint8_t*)d_src, size, fi.total, fi.sb, fi.nsb, 0, row_bytes);
+		const uint64_t first = 0;
+		if (const size_t e = finish_flagged_pieces(ctx, &frame, &first, 1, fi.nsb, &d_src, &size, &fi, T, d_index, nullptr, d_rows, a.sb_flags, n, P, row_bytes, d_dst,
+							   dst_stride, stream))
+			return e;
 	}
 	return n * row_bytes;
 }

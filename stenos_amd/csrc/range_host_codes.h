@@ -3,7 +3,10 @@
 // lo, hi, dst}; the superblock is fetched and inflated on the host, then the piece is copied out (code 2), cut out of the
 // superblock as the byte kernels rebuild it (codes 3, 4), or decoded by a one-unit launch of decode_ranges over the inflated
 // block stream (code 5).  Consecutive pieces of one superblock share the fetch and the inflation.  Slow.
+// Behind it the tail both gather calls end with (gather_host.cpp, gather_batch_host.cpp): finish_flagged_pieces.
 #pragma once
+#include <algorithm>
+
 #include "frame_access.h"
 #include "range.h"
 
@@ -117,5 +120,60 @@ struct HostCodes {
 		return *back ? (size_t)STENOS_ERROR_INVALID_INPUT : 0;
 	}
 };
+
+// The host tail of the gather calls, after a status word with DECODE_STATUS_HOST_CODES: the pairs and the flags of the
+// superblocks come down into h_gtab (d_ids == NULL: every pair is of frame 0, and two copies instead of three; one wait), every
+// row is cut again with the kernels' own cutting function, the pieces of flagged superblocks are kept, ordered by (frame,
+// superblock) and finished, one HostCodes per frame that has any.  h_frames, h_first: the call's frame table and numbering (m
+// frames, S superblocks); frame f's pointer, size and FrameInfo at [f]; its offsets start at d_index + h_first[f] + f.
+// Returns 0 or an error code.  Slow.
+inline size_t finish_flagged_pieces(stenos_context_s* ctx, const codec::GatherFrame* h_frames, const uint64_t* h_first, size_t m, uint64_t S, const void* const* d_frames,
+				    const size_t* sizes, const FrameInfo* info, size_t T, const uint64_t* d_index, const uint64_t* d_ids, const uint64_t* d_rows,
+				    const uint32_t* d_flags, size_t n, uint64_t P, size_t row_bytes, void* d_dst, size_t dst_stride, hipStream_t stream)
+{
+	if (!zstd().ok)
+		return STENOS_ERROR_ZSTD_INTERNAL;
+	const size_t o_hrows = d_ids ? align64(n * 8) : 0, o_hflags = o_hrows + align64(n * 8);
+	if (!ctx->h_gtab.ensure(o_hflags + S * 4) || !ctx->rtab.ensure(128) || !ctx->h_rtab.ensure(128))
+		return STENOS_ERROR_ALLOC;
+	uint64_t* const h_ids = (uint64_t*)ctx->h_gtab.data();
+	uint64_t* const h_rows = (uint64_t*)(ctx->h_gtab.data() + o_hrows);
+	uint32_t* const h_flags = (uint32_t*)(ctx->h_gtab.data() + o_hflags);
+	if ((d_ids && hipMemcpyAsync(h_ids, d_ids, n * 8, hipMemcpyDeviceToHost, stream) != hipSuccess) ||
+	    hipMemcpyAsync(h_rows, d_rows, n * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+	    hipMemcpyAsync(h_flags, d_flags, S * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+		(void)hipStreamSynchronize(stream);
+		return STENOS_ERROR_UNDEFINED;
+	}
+	struct FrameUnit {
+		uint64_t frame;
+		RangeUnit u;
+	};
+	std::vector<FrameUnit> units;
+	for (uint64_t i = 0; i < n; ++i)
+		for (uint64_t j = 0; j < P; ++j) {
+			uint64_t g;
+			codec::GatherPiece p;
+			FrameUnit x;
+			x.frame = d_ids ? h_ids[i] : 0;
+			if (codec::gather_cut_pair(h_frames, m, row_bytes, dst_stride, x.frame, h_rows[i], i, j, &g, &p) != codec::GATHER_PAIR_PIECE || !h_flags[g])
+				continue;
+			x.u.dst = (uint8_t*)d_dst + p.dst;
+			x.u.sb = (uint32_t)(g - h_first[x.frame]);
+			x.u.lo = p.lo;
+			x.u.hi = p.hi;
+			x.u.unused = 0;
+			units.push_back(x);
+		}
+	std::stable_sort(units.begin(), units.end(), [](const FrameUnit& x, const FrameUnit& y) { return x.frame != y.frame ? x.frame < y.frame : x.u.sb < y.u.sb; });
+	for (size_t k = 0; k < units.size();) {
+		const uint64_t f = units[k].frame;
+		HostCodes hc(ctx, d_frames[f], sizes[f], T, d_index + h_first[f] + f, info[f], stream);
+		for (; k < units.size() && units[k].frame == f; ++k)
+			if (size_t err = hc.finish(units[k].u))
+				return err;
+	}
+	return 0;
+}
 
 } // namespace stenos_host

@@ -1,6 +1,7 @@
-// tests/emul_gather/emul_gather.cpp -- TEST INFRASTRUCTURE.  The cutting function and decode_superblock_pieces
-// (stenos_amd/csrc/gather_codec.h) compiled for the host with WV_HOST_EMULATION, as tests/emul_ranges compiles
-// decode_superblock_window: 64 lanes in lockstep, LDS as a plain buffer.  The shipped library never contains or calls this.
+// tests/emul_gather/emul_gather.cpp -- TEST INFRASTRUCTURE.  The cutting function, decode_superblock_pieces and the chunk rule
+// of the gather kernels, decode_gather_chunk (stenos_amd/csrc/gather_codec.h), compiled for the host with WV_HOST_EMULATION,
+// as tests/emul_ranges compiles decode_superblock_window: 64 lanes in lockstep, LDS as a plain buffer.  The shipped library
+// never contains or calls this.
 #define WV_HOST_EMULATION 1
 #include "../../stenos_amd/csrc/gather_codec.h"
 
@@ -14,13 +15,14 @@ enum { GUARD = 64, GUARD_BYTE = 0xA5 };
 
 namespace {
 // One read arena: the piece table (16-byte entries), then the payload, shifted off its 16-byte boundary by `misalign`.
-// One write arena: a guard, then per piece its slot and a guard; the arena itself is shifted by dst_misalign.
+// One write arena: a guard, then per piece its slot and a guard, then (flag_word) the superblock's flag word and a guard; the
+// arena itself is shifted by dst_misalign.
 struct Arenas {
 	uint8_t *lds = nullptr, *rd = nullptr, *wr = nullptr;
-	uint8_t *tab = nullptr, *from = nullptr, *to = nullptr;
+	uint8_t *tab = nullptr, *from = nullptr, *to = nullptr, *flag = nullptr;
 	size_t rd_bytes = 0, wr_bytes = 0;
 	DecLayout L;
-	bool make(const uint8_t* src, size_t csize, size_t T, const uint32_t* lo, const uint32_t* hi, size_t count, int misalign, int dst_misalign)
+	bool make(const uint8_t* src, size_t csize, size_t T, const uint32_t* lo, const uint32_t* hi, size_t count, int misalign, int dst_misalign, bool flag_word = false)
 	{
 		L = make_dec_layout((uint32_t)T);
 		const size_t tab_bytes = count * sizeof(GatherPiece);
@@ -28,6 +30,7 @@ struct Arenas {
 		wr_bytes = GUARD;
 		for (size_t k = 0; k < count; ++k)
 			wr_bytes += (hi[k] > lo[k] ? hi[k] - lo[k] : 0) + GUARD;
+		wr_bytes += flag_word ? 4 + GUARD : 0;
 		// (larger than the regions by a margin nothing relies on)
 		if (posix_memalign((void**)&lds, 64, L.total + 256) || posix_memalign((void**)&rd, 64, rd_bytes + 128) || posix_memalign((void**)&wr, 64, wr_bytes + 128))
 			return false;
@@ -47,10 +50,12 @@ struct Arenas {
 			memcpy(tab + k * sizeof p, &p, sizeof p);
 			at += (hi[k] > lo[k] ? hi[k] - lo[k] : 0) + GUARD;
 		}
+		flag = flag_word ? to + at : nullptr;
 		return true;
 	}
-	// the slots' bytes, back to back, to out; false: a byte outside the slots changed
-	bool collect(const uint32_t* lo, const uint32_t* hi, size_t count, uint8_t* out) const
+	// the slots' bytes, back to back, to out, and the flag word (four guard bytes where nothing wrote it) to *flag_out; false: a
+	// byte outside the slots and the flag word changed
+	bool collect(const uint32_t* lo, const uint32_t* hi, size_t count, uint8_t* out, uint32_t* flag_out = nullptr) const
 	{
 		const uint8_t* p = wr;
 		for (; p < to + GUARD; ++p)
@@ -65,6 +70,12 @@ struct Arenas {
 				if (*p != GUARD_BYTE)
 					return false;
 		}
+		if (flag) {
+			memcpy(flag_out, p, 4);
+			for (const uint8_t* e = (p += 4) + GUARD; p < e; ++p)
+				if (*p != GUARD_BYTE)
+					return false;
+		}
 		for (; p < wr + wr_bytes + 128; ++p)
 			if (*p != GUARD_BYTE)
 				return false;
@@ -74,6 +85,11 @@ struct Arenas {
 	{
 		const LanePieces q = load_pieces(tab, (uint32_t)count);
 		return decode_superblock_pieces(lds, L, (uint32_t)T, from, (uint32_t)csize, (uint32_t)dsize, q, to);
+	}
+	// the chunk rule on the frame at `from`: superblock s, whose header the index puts at p
+	uint32_t run_chunk(size_t size, size_t T, uint64_t total, uint64_t sb, uint64_t s, uint64_t p, size_t count)
+	{
+		return decode_gather_chunk<0>(lds, (uint32_t)T, from, size, total, sb, s, p, tab, (uint32_t)count, to, (uint32_t*)flag);
 	}
 	~Arenas()
 	{
@@ -121,6 +137,20 @@ size_t emul_gather_pieces(const uint8_t* src, size_t csize, size_t T, size_t dsi
 	return r == DEC_ERROR ? (size_t)-4 : 0;
 }
 
+// ---- the chunk rule ----
+// Superblock s of the frame src[0, size) (an array of `total` bytes in superblocks of sb) with the index entry p and `count`
+// (1..64) pieces -> out, back to back; *flag: the superblock's flag word, 0xA5A5A5A5 where it was not written.  Returns the
+// DECODE_STATUS_* bits of the chunk, (size_t)-7 if a byte outside the slots and the flag word changed.
+size_t emul_gather_chunk(const uint8_t* src, size_t size, size_t T, uint64_t total, uint64_t sb, uint64_t s, uint64_t p, const uint32_t* lo, const uint32_t* hi,
+			 size_t count, uint8_t* out, uint32_t* flag, int misalign, int dst_misalign)
+{
+	Arenas b;
+	if (count == 0 || count > 64 || !b.make(src, size, T, lo, hi, count, misalign, dst_misalign, true))
+		return (size_t)-3;
+	const uint32_t r = b.run_chunk(size, T, total, sb, s, p, count);
+	return b.collect(lo, hi, count, out, flag) ? r : (size_t)-7;
+}
+
 #ifdef WV_AUDIT
 // The same with every memory access of the kernel source checked (wavevec_host.h, "the access audit"):
 //   LDS           the wave's make_dec_layout(T).total bytes, nothing behind them;
@@ -129,22 +159,21 @@ size_t emul_gather_pieces(const uint8_t* src, size_t csize, size_t T, size_t dsi
 // report: as emul_audit_window_decompress (tests/emul_ranges).
 static const char* g_audit_first_name = "";
 const char* emul_audit_first_name(void) { return g_audit_first_name; }
-size_t emul_audit_gather_pieces(const uint8_t* src, size_t csize, size_t T, size_t dsize, const uint32_t* lo, const uint32_t* hi, size_t count, uint8_t* out,
-				int misalign, int dst_misalign, uint64_t* report)
+static void audit_on(const Arenas& b, size_t read_bytes)
 {
-	Arenas b;
-	if (count == 0 || count > 64 || !b.make(src, csize, T, lo, hi, count, misalign, dst_misalign))
-		return (size_t)-3;
 	wv::AuditState& A = wv::audit_state();
 	memset(&A, 0, sizeof A);
 	A.lo[wv::WV_AUDIT_LDS] = b.lds;
 	A.hi[wv::WV_AUDIT_LDS] = b.lds + b.L.total;
 	A.lo[wv::WV_AUDIT_GREAD] = b.rd;
-	A.hi[wv::WV_AUDIT_GREAD] = (const uint8_t*)(((uintptr_t)b.from + csize + 15) & ~(uintptr_t)15);
+	A.hi[wv::WV_AUDIT_GREAD] = (const uint8_t*)(((uintptr_t)b.from + read_bytes + 15) & ~(uintptr_t)15);
 	A.lo[wv::WV_AUDIT_GWRITE] = b.to;
 	A.hi[wv::WV_AUDIT_GWRITE] = b.to + b.wr_bytes;
 	A.on = true;
-	const uint32_t r = b.run(csize, T, dsize, count);
+}
+static void audit_off(uint64_t* report)
+{
+	wv::AuditState& A = wv::audit_state();
 	A.on = false;
 	report[0] = A.violations;
 	report[1] = A.checked;
@@ -152,9 +181,31 @@ size_t emul_audit_gather_pieces(const uint8_t* src, size_t csize, size_t T, size
 	report[3] = (uint64_t)A.first_off;
 	report[4] = A.first_width;
 	g_audit_first_name = A.first_name ? A.first_name : "";
+}
+size_t emul_audit_gather_pieces(const uint8_t* src, size_t csize, size_t T, size_t dsize, const uint32_t* lo, const uint32_t* hi, size_t count, uint8_t* out,
+				int misalign, int dst_misalign, uint64_t* report)
+{
+	Arenas b;
+	if (count == 0 || count > 64 || !b.make(src, csize, T, lo, hi, count, misalign, dst_misalign))
+		return (size_t)-3;
+	audit_on(b, csize);
+	const uint32_t r = b.run(csize, T, dsize, count);
+	audit_off(report);
 	if (!b.collect(lo, hi, count, out))
 		return (size_t)-7;
 	return r == DEC_ERROR ? (size_t)-4 : 0;
+}
+// ... and the chunk rule: the global reads end with the 16-byte hull of the frame, the flag word lies in the write arena
+size_t emul_audit_gather_chunk(const uint8_t* src, size_t size, size_t T, uint64_t total, uint64_t sb, uint64_t s, uint64_t p, const uint32_t* lo, const uint32_t* hi,
+			       size_t count, uint8_t* out, uint32_t* flag, int misalign, int dst_misalign, uint64_t* report)
+{
+	Arenas b;
+	if (count == 0 || count > 64 || !b.make(src, size, T, lo, hi, count, misalign, dst_misalign, true))
+		return (size_t)-3;
+	audit_on(b, size);
+	const uint32_t r = b.run_chunk(size, T, total, sb, s, p, count);
+	audit_off(report);
+	return b.collect(lo, hi, count, out, flag) ? r : (size_t)-7;
 }
 #endif
 

@@ -1,6 +1,7 @@
 """CPU-side checks of stenos_hip_gather_rows (include/stenos_hip.h): the cutting function of csrc/gather_codec.h against a Python
 model; decode_superblock_pieces in the host emulation (tests/emul_gather: plain and with the access audit) against slices of the
-oracle's decode; declared, exported and bound; the refusals that need no device; loud failure without one; the build properties of
+oracle's decode; the chunk rule of the gather kernels, decode_gather_chunk, in the same emulation on a frame built by hand;
+declared, exported and bound; the refusals that need no device; loud failure without one; the build properties of
 gather_decode (csrc/gather_kernels.hip).
 
 Every chunk of pieces is decoded twice: by the plain build (LDS filled with 0xCD) and by the audited one (LDS filled with 0x37;
@@ -36,6 +37,8 @@ def _load(name):
     U32P = ctypes.POINTER(ctypes.c_uint32)
     lib.emul_gather_pieces.restype = c_size_t
     lib.emul_gather_pieces.argtypes = [c_void_p, c_size_t, c_size_t, c_size_t, U32P, U32P, c_size_t, c_void_p, c_int, c_int]
+    lib.emul_gather_chunk.restype = c_size_t
+    lib.emul_gather_chunk.argtypes = [c_void_p, c_size_t, c_size_t] + [c_uint64] * 4 + [U32P, U32P, c_size_t, c_void_p, U32P, c_int, c_int]
     lib.emul_set_lds_fill.restype = None
     lib.emul_set_lds_fill.argtypes = [c_int]
     lib.emul_gather_pieces_per_row.restype = c_uint64
@@ -59,6 +62,8 @@ def audit():
     lib = _load("libstenos_emul_gather_audit.so")
     lib.emul_audit_gather_pieces.restype = c_size_t
     lib.emul_audit_gather_pieces.argtypes = lib.emul_gather_pieces.argtypes + [ctypes.POINTER(c_uint64)]
+    lib.emul_audit_gather_chunk.restype = c_size_t
+    lib.emul_audit_gather_chunk.argtypes = lib.emul_gather_chunk.argtypes + [ctypes.POINTER(c_uint64)]
     lib.emul_audit_first_name.restype = c_char_p
     lib.emul_set_lds_fill(0x37)
     return lib
@@ -303,6 +308,101 @@ def test_truncated_in_front_is_an_error_and_damage_behind_is_not_seen(plain, aud
         # ... while a chunk with one piece that reaches into it sees it
         r, _ = gather(plain, audit, bad, len(payload), T, data.size, near + [(2 * bs, 1)], 0, 0)
         assert r == DECODE_ERROR, (T, kinds, r)
+
+
+# ---- the chunk rule ------------------------------------------------------------------------------------------------------
+
+TRUNCATED, INVALID, HOST_CODES = 1, 2, 4  # DECODE_STATUS_* (csrc/kernels.h)
+UNTOUCHED = 0xA5A5A5A5  # the flag word as the arena is filled
+
+
+def chunk(plain, audit, frame, size, T, total, sb, s, p, pieces, mis, dmis):
+    """decode_gather_chunk on superblock s of frame[:size] with the index entry p -> (status, flag word, the slots' bytes) of the
+    plain build; the audited build must agree, and neither may touch a byte outside the slots and the flag word"""
+    count = len(pieces)
+    U = ctypes.c_uint32 * count
+    lo, hi = U(*[q[0] for q in pieces]), U(*[q[0] + q[1] for q in pieces])
+    nbytes = sum(q[1] for q in pieces)
+    outs = []
+    for lib in (plain, audit):
+        out = np.zeros(nbytes + 16, dtype=np.uint8)
+        flag = ctypes.c_uint32(0)
+        args = [np_ptr(frame), size, T, total, sb, s, p, lo, hi, count, np_ptr(out), ctypes.byref(flag), mis, dmis]
+        if lib is plain:
+            r = lib.emul_gather_chunk(*args)
+        else:
+            rep = (c_uint64 * 5)()
+            r = lib.emul_audit_gather_chunk(*args, rep)
+            off = rep[3] - (1 << 64) if rep[3] >> 63 else rep[3]
+            assert rep[0] == 0, (f"s={s} p={p:#x} size={size} mis={mis}/{dmis}: {rep[0]} accesses outside their arena, first: "
+                                 f"{lib.emul_audit_first_name().decode()} kind {rep[2]} (0 LDS, 1 global read, 2 global write) at arena offset {off}, {rep[4]} bytes")
+        assert r != E(7), f"s={s} p={p:#x} size={size} mis={mis}/{dmis}: a byte outside the slots and the flag word changed"
+        assert r != E(3)
+        outs.append((r, flag.value, out[:nbytes].copy()))
+    assert outs[0][:2] == outs[1][:2] and np.array_equal(outs[0][2], outs[1][2]), (s, p, "the result depends on the LDS contents or the build")
+    return outs[0]
+
+
+def test_chunk_rule_on_a_frame(oracle, plain, audit):
+    """What a gather wavefront does with its superblock (csrc/gather_codec.h, decode_gather_chunk: the one copy gather_decode and
+    gather_batch_decode call), on a frame of 32-bit elements with two superblocks of four blocks and a tail: the index entry and
+    the header checked against the frame, the pieces against the superblock, the dispatch on the code."""
+    T, sb, tail = 4, 4096, 1500
+    total = 2 * sb + tail
+    # superblock 0: a block stream (code 1), superblock 1: stored as it is (code 6), the tail: a block stream with a partial block
+    pay0, data0 = oracle_payload(oracle, "walk", T, sb, 71)
+    data1 = np.random.default_rng(72).integers(0, 256, sb, dtype=np.uint8)
+    pay2, data2 = oracle_payload(oracle, "dict16", T, tail, 73)
+    array = np.concatenate([data0, data1, data2])
+    head = lambda code, n: bytes([code]) + n.to_bytes(3, "little")  # noqa: E731
+    parts = [b"\xff" + total.to_bytes(7, "little") + sb.to_bytes(4, "little"), head(1, len(pay0)) + pay0, head(6, sb) + data1.tobytes(), head(1, len(pay2)) + pay2]
+    index = list(itertools.accumulate(len(x) for x in parts))  # index[s]: the header of superblock s; index[3]: the frame's end
+    size = index[3]
+    frame = padded(b"".join(parts))
+    turn = itertools.count(5)
+    mis = lambda: MISALIGN[next(turn) % len(MISALIGN)]  # noqa: E731
+    pieces = [[(0, 1), (5, 300), (1020, 2100), (sb - 1, 1), (0, sb)], [(0, sb), (17, 4000), (sb - 1, 1), (3, 1)], [(0, tail), (tail - 1, 1), (1000, 500), (7, 9)]]
+    want = lambda s, ps: np.concatenate([array[s * sb + lo:s * sb + lo + n] for lo, n in ps])  # noqa: E731
+
+    def run(s, p, ps=None, fr=frame, sz=size):
+        return chunk(plain, audit, fr, sz, T, total, sb, s, p, ps or pieces[s], *mis())
+
+    def refused(got, status, ps):  # nothing delivered, no flag set
+        assert got[0] == status and got[1] == UNTOUCHED and (got[2] == 0xA5).all(), (got[0], hex(got[1]), ps[:2])
+
+    # code 1 and code 6 delivered, the tail too
+    for s in range(3):
+        st, flag, got = run(s, index[s])
+        assert st == 0 and flag == UNTOUCHED and np.array_equal(got, want(s, pieces[s])), (s, st, hex(flag))
+    # an index entry equal to the frame size, three bytes in front of its end, and 2^63: no header is read
+    for p in (size, size - 3, 1 << 63):
+        refused(run(2, p), TRUNCATED, pieces[2])
+    # (four bytes in front of the end a header is read: whatever stands there, its payload cannot fit or its code is refused)
+    assert run(2, size - 4)[0] in (TRUNCATED, INVALID)
+    # a csize that runs one byte past the frame
+    refused(run(2, index[2], sz=size - 1), TRUNCATED, pieces[2])
+    # code 6 with csize != dsize
+    bad = frame.copy()
+    bad[index[1] + 1:index[1] + 4] = np.frombuffer((sb - 1).to_bytes(3, "little"), dtype=np.uint8)
+    refused(run(1, index[1], fr=bad), INVALID, pieces[1])
+    # codes 2-5 are the host's: the flag word is set, nothing is delivered
+    for code in (2, 3, 4, 5):
+        bad = frame.copy()
+        bad[index[0]] = code
+        st, flag, got = run(0, index[0], fr=bad)
+        assert st == HOST_CODES and flag == 1 and (got == 0xA5).all(), (code, st, hex(flag))
+    # codes 0 and 7 are none
+    for code in (0, 7, 255):
+        bad = frame.copy()
+        bad[index[1]] = code
+        refused(run(1, index[1], fr=bad), INVALID, pieces[1])
+    # a superblock number whose begin is at or past the array's end (3 sb > total; the largest number a table can hold)
+    for s in (3, (1 << 32) - 1):
+        refused(run(s, index[2], ps=pieces[2]), INVALID, pieces[2])
+    # a piece with hi > dsize, among good ones; and one with lo > hi cannot be built here (its slot would be negative)
+    for s, dsize in ((0, sb), (1, sb), (2, tail)):
+        ps = pieces[s][:2] + [(dsize - 10, 11)]
+        refused(run(s, index[s], ps=ps), INVALID, ps)
 
 
 # ---- the entry point --------------------------------------------------------------------------------------------------

@@ -231,6 +231,59 @@ def test_index_forms():
         hi.close()
 
 
+def test_long_chains_through_the_shared_front_end(hooks_lib):
+    """Frames of exactly 256 and 257 superblocks -- the two sides of kBatchSerialWalkMax (csrc/frame_access.h): the first is walked
+    by the serial batched walk, the second by a parallel walk of its own --, one of 3 superblocks and a few bytes, and an empty
+    array, through the three calls that share the front end of csrc/frame_batch.h: the index of stenos_hip_frames_index is the
+    frames' own indices one after the other, stenos_hip_gather_rows_batch delivers the rows with and without it, and
+    stenos_hip_decompress_batch returns the arrays.  Then all of it again with every chain walked by one lane (the test build's
+    stenos_hip_test_walk): the same index words.  Level 0 and the small superblock: every superblock is a copy."""
+    torch = _cuda()
+    T, rb = 4, 100  # (rows of 100 bytes straddle the superblocks' boundaries)
+    sb = _sb(T, SHIFT)
+    make, st, other = Stenos(0, lib=hooks_lib), Stenos(1, lib=hooks_lib), Stenos(1, lib=hooks_lib)
+    try:
+        assert make.lib.stenos_set_block_size(make.ctx, SHIFT) == 0
+        rng = np.random.default_rng(77)
+        bt = Batch()
+        for nbytes in (256 * sb, 257 * sb, 3 * sb + 20):
+            bt.add_single(make, torch, T, rng.integers(0, 256, nbytes, dtype=np.uint8), sb)
+        bt.add_empty(torch)
+        # (a second context makes the single frames' indices: the first one's index buffer is what is under test)
+        singles = [other.frame_index(f, T, c) if d.size else [8] for f, c, d in zip(bt.frames, bt.csizes, bt.datas)]
+        assert [len(s) - 1 for s in singles] == [256, 257, 4, 0]
+        nrows = [d.size // rb for d in bt.datas]
+        # the first and last row of every frame that has rows; in the long frame the rows of superblocks 255 and 256 and the one
+        # that straddles their boundary; random ones
+        pairs = [(f, r) for f in range(3) for r in (0, nrows[f] - 1)]
+        pairs += [(1, r) for r in (255 * sb // rb + 1, 256 * sb // rb, 256 * sb // rb + 1, 257 * sb // rb - 1)]
+        assert (256 * sb) % rb and (256 * sb // rb + 1) * rb <= 257 * sb
+        pairs += [(int(f), int(rng.integers(0, nrows[f]))) for f in rng.integers(0, 3, 300)]
+        fids, rows = [f for f, _ in pairs], [r for _, r in pairs]
+        words = []
+        for serial in (False, True):
+            assert st.lib.stenos_hip_test_walk(st.ctx, 1 if serial else 0) in (-1, 0)
+            p, entries = st.frames_index(bt.frames, T, bt.csizes)
+            assert entries == sum(len(s) for s in singles)
+            words.append(_device_words(p, entries))
+            assert words[-1] == [x for s in singles for x in s], serial
+            bt.gather(st, torch, T, rb, fids, rows)  # (walks the chains itself)
+            p, entries = st.frames_index(bt.frames, T, bt.csizes)
+            bt.gather(st, torch, T, rb, fids, rows, p, rb + 67, 5)
+            assert _device_words(p, entries) == words[-1]
+            dsts = [torch.full((max(d.size, 8),), GUARD_BYTE, dtype=torch.uint8, device="cuda") for d in bt.datas]
+            assert st.decompress_batch(bt.frames, T, bt.csizes, dsts) == [d.size for d in bt.datas]
+            for d, dst in zip(bt.datas, dsts):
+                assert np.array_equal(dst[:d.size].cpu().numpy(), d) and (dst[d.size:] == GUARD_BYTE).all().item()
+            if not serial:  # (the flag the last parallel walk left: it did not fall back to one lane)
+                assert st.lib.stenos_hip_test_walk(st.ctx, 0) == 0
+        assert words[0] == words[1]
+    finally:
+        st.lib.stenos_hip_test_walk(st.ctx, 0)
+        for s in (make, st, other):
+            s.close()
+
+
 def test_invalid_pairs():
     """a frame number equal to m, one of 2^63, and the row the small frame refuses though a larger frame of the batch accepts it:
     INVALID_PARAMETER, that slot untouched, every gap intact; without the pair the call is correct"""
