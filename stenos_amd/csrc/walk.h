@@ -156,6 +156,161 @@ WALK_HD void scan_window16(const Plan& P, const uint8_t* frame, uint32_t k, uint
 		}
 	}
 }
+// ---- phase A as walk_speculate runs it: scan_window16 cut into its parts --------------------------------------------
+// The same roots as scan_window16 (the same set, the same count; tests/emul_walk_scan replays both on the same windows), but
+//   * the bytes of a step are loaded apart from their test (scan_load16), so that a lane can have several steps' loads in flight;
+//   * the filter looks at two bytes of a position, the code and the top byte of the size (scan_candidates16);
+//   * what passes the filter is not looked at on the spot, a lane at a time with the others of its wavefront waiting, twice, for
+//     memory: it goes to a list (scan_list16) that is gone through afterwards, one entry per lane, with all loads in flight
+//     (scan_deferred).  A full list sends a candidate to its exact test at once: the result does not depend on the list's size.
+#ifndef STENOS_WALK_SCAN_STEPS
+#define STENOS_WALK_SCAN_STEPS 4 // (8: 70 vector registers, seven waves per SIMD, and the 2 048 workgroups of a long frame need a second round)
+#endif
+constexpr uint32_t SCAN_STEPS = STENOS_WALK_SCAN_STEPS; // steps of 16 positions whose bytes a lane requests before it looks at the first
+constexpr uint32_t DEFER_CAP = 2048;                    // candidates that wait in the list for their exact test
+struct ScanFilter {
+	uint32_t add; // per byte: 0x7F - (the largest top size byte & 0x7F)
+	uint32_t hi;  // the largest top size byte is 128 or more
+};
+WALK_HD ScanFilter scan_filter(const Plan& P)
+{
+	const uint32_t top = (P.sb_bytes >> 16) > 255u ? 255u : (P.sb_bytes >> 16);
+	ScanFilter F;
+	F.add = (0x7Fu - (top & 0x7Fu)) * 0x01010101u;
+	F.hi = top >> 7;
+	return F;
+}
+// the 20 bytes at base, all of them inside the frame (base + 20 <= size)
+WALK_HD void scan_load16(const uint8_t* frame, uint64_t base, uint32_t* w)
+{
+	for (int i = 0; i < 5; ++i)
+		w[i] = header_word(frame, base + 4 * (uint64_t)i);
+}
+// ... and the last steps of a frame, byte by byte: zeros behind the frame's end
+WALK_HD void scan_load16_bytes(const Plan& P, const uint8_t* frame, uint64_t base, uint32_t* w)
+{
+	for (int i = 0; i < 5; ++i) {
+		w[i] = 0;
+		for (int b = 0; b < 4; ++b) {
+			const uint64_t q = base + 4 * (uint64_t)i + (uint64_t)b;
+			if (q < P.size)
+				w[i] |= (uint32_t)frame[q] << (8 * b);
+		}
+	}
+}
+// Bit j: position base + j may hold a plausible header -- its code byte is in 1..8 and the top byte of its size is at most
+// that of the superblock size.  A superset of plausible(); about one payload byte in 2 000 passes where 3 % pass the code alone.
+WALK_HD uint32_t scan_candidates16(ScanFilter F, const uint32_t* w)
+{
+	uint32_t f[4], any = 0;
+	for (int i = 0; i < 4; ++i) {
+		const uint32_t y = (w[i] | 0x80808080u) - 0x01010101u; // per byte (b - 1) mod 128, no borrow between bytes
+		const uint32_t c = (y & 0x78787878u) + 0x78787878u;    // bit 7: (b - 1) mod 128 is 8 or more; with bit 7 of b itself: b is not in 1..8
+		const uint32_t t = (w[i] >> 24) | (w[i + 1] << 8);     // the bytes three positions on
+		const uint32_t s = (t & 0x7F7F7F7Fu) + F.add;          // bit 7: the low seven bits are above the bound's
+		const uint32_t gt = F.hi ? t & s : t | s;              // bit 7: the byte is above the bound
+		f[i] = ~(c | w[i] | gt) & 0x80808080u;
+		any |= f[i];
+	}
+	if (!any) // (nearly always: the bits are put together for the few)
+		return 0;
+	uint32_t cand = 0;
+	for (int i = 0; i < 4; ++i)
+		cand |= (((f[i] >> 7) & 1u) | ((f[i] >> 14) & 2u) | ((f[i] >> 21) & 4u) | ((f[i] >> 28) & 8u)) << (4 * i);
+	return cand;
+}
+// The exact test of position p, as scan_window16 makes it: a root when it is inside the window and holds a plausible header that
+// hops out of the window onto another plausible header, or onto the frame's end.
+template <class Add>
+WALK_HD void scan_test(const Plan& P, const uint8_t* frame, uint32_t k, uint64_t p, uint64_t* roots, uint32_t* nroots, Add add)
+{
+	const uint64_t wend = seg_begin(P, k) + P.window;
+	if (p >= wend || !readable(P, p))
+		return;
+	const uint32_t h = header_word(frame, p);
+	const uint64_t q = hop(p, h);
+	if (!plausible(P, h) || q < wend)
+		return;
+	if (readable(P, q) ? !plausible(P, header_word(frame, q)) : q != P.size)
+		return;
+	const uint32_t idx = add(nroots);
+	if (idx < LANES)
+		roots[idx] = p;
+}
+// The candidates among positions [base, base + 16) go to list[0..DEFER_CAP) as offsets from the segment's begin; *nlist may run
+// past DEFER_CAP: those candidates have had their exact test here.  add as for scan_window16.
+template <class Add>
+WALK_HD void scan_list16(const Plan& P, const uint8_t* frame, uint32_t k, uint64_t base, uint32_t cand, uint64_t* roots, uint32_t* nroots, uint32_t* list,
+			 uint32_t* nlist, Add add)
+{
+	const uint32_t at = (uint32_t)(base - seg_begin(P, k));
+	while (cand) {
+		const uint32_t j = (uint32_t)__builtin_ctz(cand);
+		cand &= cand - 1u;
+		const uint32_t d = add(nlist);
+		if (d < DEFER_CAP)
+			list[d] = at + j;
+		else
+			scan_test(P, frame, k, base + j, roots, nroots, add);
+	}
+}
+// One lane's share of segment k's window, for a workgroup of SCAN_THREADS lanes.  A step is 16 positions per lane, STEP_BYTES
+// for the workgroup.  The steps are taken SCAN_STEPS at a time while every lane of every one of them has the first of its 16
+// positions inside the window and its 20 bytes inside the frame: all loads of such a group are requested before the first is
+// looked at.  What is left -- the window's last positions, the last steps of a frame -- goes step by step, byte by byte where the
+// frame ends; lanes behind the window's end request nothing.
+constexpr uint32_t SCAN_THREADS = 256;
+constexpr uint32_t STEP_BYTES = SCAN_THREADS * 16u, GROUP_BYTES = SCAN_STEPS * STEP_BYTES;
+WALK_HD uint32_t scan_groups(const Plan& P, uint32_t k)
+{
+	const uint64_t begin = seg_begin(P, k);
+	const uint64_t in_frame = P.size >= begin + 4 ? P.size - begin - 4 : 0; // a group ends here at the latest: its last lane reads 4 bytes more
+	const uint64_t in_window = (uint64_t)P.window + 15u;                  // ... and here: its last lane's first position is inside the window
+	return (uint32_t)((in_frame < in_window ? in_frame : in_window) / GROUP_BYTES);
+}
+template <class Add>
+WALK_HD void scan_lane(const Plan& P, const uint8_t* frame, uint32_t k, uint32_t lane, uint64_t* roots, uint32_t* nroots, uint32_t* list, uint32_t* nlist,
+		       Add add)
+{
+	const uint64_t begin = seg_begin(P, k), wend = begin + P.window;
+	const ScanFilter F = scan_filter(P);
+	const uint32_t groups = scan_groups(P, k);
+	for (uint32_t g = 0; g < groups; ++g) {
+		const uint64_t from = begin + (uint64_t)g * GROUP_BYTES;
+		uint32_t w[SCAN_STEPS][5];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+		for (uint32_t u = 0; u < SCAN_STEPS; ++u)
+			scan_load16(frame + from, u * STEP_BYTES + lane * 16u, w[u]);
+#if defined(__HIP_DEVICE_COMPILE__)
+		__builtin_amdgcn_sched_barrier(0); // (left alone, the scheduler puts the first step's filter, and a wait, in front of the later steps' loads)
+#pragma unroll
+#endif
+		for (uint32_t u = 0; u < SCAN_STEPS; ++u) {
+			const uint32_t cand = scan_candidates16(F, w[u]);
+			if (cand)
+				scan_list16(P, frame, k, from + u * STEP_BYTES + lane * 16u, cand, roots, nroots, list, nlist, add);
+		}
+	}
+	for (uint64_t base = begin + (uint64_t)groups * GROUP_BYTES + lane * 16u; base < wend; base += STEP_BYTES) {
+		uint32_t w[5];
+		if (base + 20 <= P.size)
+			scan_load16(frame, base, w);
+		else
+			scan_load16_bytes(P, frame, base, w);
+		const uint32_t cand = scan_candidates16(F, w);
+		if (cand)
+			scan_list16(P, frame, k, base, cand, roots, nroots, list, nlist, add);
+	}
+}
+// entry i of the list (i < min(*nlist, DEFER_CAP))
+template <class Add>
+WALK_HD void scan_deferred(const Plan& P, const uint8_t* frame, uint32_t k, const uint32_t* list, uint32_t i, uint64_t* roots, uint32_t* nroots, Add add)
+{
+	scan_test(P, frame, k, seg_begin(P, k) + list[i], roots, nroots, add);
+}
+
 // one lane follows one root while the headers look like headers; false: the chain broke
 WALK_HD bool follow_root(const Plan& P, const uint8_t* frame, uint32_t k, uint64_t root, uint64_t* exit, uint32_t* hops)
 {

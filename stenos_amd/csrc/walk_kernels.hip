@@ -9,15 +9,9 @@ using namespace walk;
 
 namespace {
 
-// Serial walk of the superblock chain by one lane: off[s] = byte offset of superblock s's header.  only_if: run only when
-// *only_if is non-zero (the fallback of the parallel walk); NULL: always.
-__global__ void walk_superblocks(const uint8_t* __restrict__ frame, uint64_t size, uint64_t first, uint64_t nsb, uint64_t* __restrict__ off,
-				 uint32_t* __restrict__ status, const uint32_t* __restrict__ only_if)
+// Serial walk of the superblock chain by one lane: off[s] = byte offset of superblock s's header.
+__device__ void serial_walk(const uint8_t* __restrict__ frame, uint64_t size, uint64_t first, uint64_t nsb, uint64_t* __restrict__ off, uint32_t* __restrict__ status)
 {
-	if (threadIdx.x != 0 || blockIdx.x != 0)
-		return;
-	if (only_if && *only_if == 0)
-		return;
 	uint64_t p = first;
 	for (uint64_t s = 0; s < nsb; ++s) {
 		if (p + 4 > size) { // stenos.cpp:1126-1127
@@ -33,14 +27,21 @@ __global__ void walk_superblocks(const uint8_t* __restrict__ frame, uint64_t siz
 	if (p > size)
 		atomicOr(status, DECODE_STATUS_TRUNCATED);
 }
+// ... as a launch of its own: frames too short for segments, and the test switch.  (The fallback of the parallel walk is in walk_write.)
+__global__ void walk_superblocks(const uint8_t* __restrict__ frame, uint64_t size, uint64_t first, uint64_t nsb, uint64_t* __restrict__ off,
+				 uint32_t* __restrict__ status)
+{
+	if (threadIdx.x == 0 && blockIdx.x == 0)
+		serial_walk(frame, size, first, nsb, off, status);
+}
 
 struct SharedAdd {
 	__device__ uint32_t operator()(uint32_t* c) const { return atomicAdd(c, 1u); }
 };
 
 // phase A: one workgroup per segment -- four wavefronts look through the window, the first one follows the roots
-constexpr uint32_t SCAN_THREADS = 256;
-__global__ __launch_bounds__(SCAN_THREADS) void walk_speculate(Plan P, const uint8_t* __restrict__ frame, Segment* __restrict__ seg, uint32_t* __restrict__ flags)
+// (eight waves per SIMD: the 2 048 workgroups of a long frame are resident in one round)
+__global__ __launch_bounds__(SCAN_THREADS, 8) void walk_speculate(Plan P, const uint8_t* __restrict__ frame, Segment* __restrict__ seg, uint32_t* __restrict__ flags)
 {
 	const uint32_t k = blockIdx.x, lane = threadIdx.x;
 	if (k == 0) {
@@ -53,13 +54,17 @@ __global__ __launch_bounds__(SCAN_THREADS) void walk_speculate(Plan P, const uin
 	if (k + 1 >= P.nseg) // the last segment is walked in phase B
 		return;
 	__shared__ uint64_t roots[LANES];
-	__shared__ uint32_t nroots;
+	__shared__ uint32_t nroots, nlist;
+	__shared__ uint32_t list[DEFER_CAP];
 	if (lane == 0)
-		nroots = 0;
+		nroots = nlist = 0;
 	__syncthreads();
-	const uint64_t begin = seg_begin(P, k), wend = begin + P.window;
-	for (uint64_t base = begin + lane * 16u; base < wend; base += SCAN_THREADS * 16u)
-		scan_window16(P, frame, k, base, roots, &nroots, SharedAdd());
+	scan_lane(P, frame, k, lane, roots, &nroots, list, &nlist, SharedAdd());
+	__syncthreads();
+	// the exact test of the candidates: one per lane, all loads in flight
+	const uint32_t listed = nlist < DEFER_CAP ? nlist : DEFER_CAP;
+	for (uint32_t i = lane; i < listed; i += SCAN_THREADS)
+		scan_deferred(P, frame, k, list, i, roots, &nroots, SharedAdd());
 	__syncthreads();
 	if (lane >= LANES)
 		return;
@@ -104,13 +109,16 @@ __global__ __launch_bounds__(64) void walk_verify(Plan P, const uint8_t* __restr
 		atomicOr(flags, WALK_FAILED);
 }
 
-// phase C: one wavefront per segment (64 lanes sum the counts in front, lane 0 writes)
+// phase C: one wavefront per segment (64 lanes sum the counts in front, lane 0 writes); and the fallback
 __global__ __launch_bounds__(64) void walk_write(Plan P, const uint8_t* __restrict__ frame, const Segment* __restrict__ seg, const uint32_t* __restrict__ flags,
 						 uint64_t* __restrict__ off, uint32_t* __restrict__ status)
 {
-	if (*flags)
-		return;
 	const uint32_t k = blockIdx.x, lane = threadIdx.x;
+	if (*flags) { // the speculation did not hold: the serial walk after all, by the first lane of the grid
+		if (k == 0 && lane == 0)
+			serial_walk(frame, P.size, P.first, P.nsb, off, status);
+		return;
+	}
 	uint64_t sum = 0;
 	for (uint32_t j = lane; j < k; j += LANES)
 		sum += seg[j].count;
@@ -130,7 +138,7 @@ hipError_t stenos_k_launch_walk(const uint8_t* frame, uint64_t size, uint64_t fi
 {
 	const Plan P = make_plan(first, size, nsb, sb_bytes);
 	if (P.nseg == 0 || !scratch) {
-		hipLaunchKernelGGL(walk_superblocks, dim3(1), dim3(64), 0, stream, frame, size, first, nsb, off, status, (const uint32_t*)nullptr);
+		hipLaunchKernelGGL(walk_superblocks, dim3(1), dim3(64), 0, stream, frame, size, first, nsb, off, status);
 		return hipGetLastError();
 	}
 	uint32_t* flags = (uint32_t*)scratch;
@@ -138,7 +146,6 @@ hipError_t stenos_k_launch_walk(const uint8_t* frame, uint64_t size, uint64_t fi
 	hipLaunchKernelGGL(walk_speculate, dim3(P.nseg), dim3(SCAN_THREADS), 0, stream, P, frame, seg, flags);
 	hipLaunchKernelGGL(walk_verify, dim3((P.nseg + 63) / 64), dim3(64), 0, stream, P, frame, seg, flags);
 	hipLaunchKernelGGL(walk_write, dim3(P.nseg), dim3(64), 0, stream, P, frame, (const Segment*)seg, (const uint32_t*)flags, off, status);
-	hipLaunchKernelGGL(walk_superblocks, dim3(1), dim3(64), 0, stream, frame, size, first, nsb, off, status, (const uint32_t*)flags);
 	return hipGetLastError();
 }
 size_t stenos_k_walk_scratch_bytes() { return 64 + (size_t)MAX_SEGMENTS * sizeof(Segment); }
