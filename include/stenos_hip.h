@@ -285,6 +285,85 @@ STENOS_EXPORT size_t stenos_hip_update_rows(stenos_context* ctx, const void* d_f
 					    const uint64_t* d_rows, const void* d_src, size_t src_stride, void* d_out, size_t out_size, const uint64_t* d_index,
 					    void* stream);
 
+/* Rows of MANY frames replaced in one call: the mirror image of stenos_hip_gather_rows_batch, with the rules of
+ * stenos_hip_update_rows applied frame by frame.  d_frames, sizes, d_outs, out_sizes and results are host arrays of m;
+ * d_frame_ids, d_rows (n each) and the source rows are device memory, which the host never reads on the common path; every
+ * enqueued step is ordered on `stream`.  The row_bytes bytes at d_src + i * src_stride replace row d_rows[i] of the array of
+ * frame d_frame_ids[i].  d_outs[f] receives a complete frame for EVERY listed frame -- one that no pair names gets a byte copy
+ * of its input -- and results[f] its size; the call returns 0 when it ran, or an error code for the call as a whole (there is
+ * no success of some frames).  n == 0 copies every frame, after the header and index checks.  Input frames are never modified;
+ * the outputs must overlap nothing: no input frame, no source row, no other output.  Two entries of d_frames may name the same
+ * frame: each entry is updated on its own, by the pairs that carry its number.  The frame of an empty array is accepted: it has
+ * no valid row and is copied.
+ * THE OUTPUT FRAMES: d_outs[f] holds, byte for byte and in size, what stenos_hip_update_rows leaves for frame f given only the
+ * pairs that name f -- so for inputs made by stenos_hip_compress or stenos_hip_compress_batch at ctx's level into destinations
+ * of the bound's size, the frame stenos_hip_compress makes of the updated array (the conditions are the single call's).
+ * WRITES TO d_outs: all or nothing.  On success nothing outside [d_outs[f], d_outs[f] + results[f]).  On any error -- a
+ * host-side refusal, an invalid pair, a refused index, a decode error in a touched superblock of any frame, a new frame that
+ * does not fit its out_sizes[f] (STENOS_ERROR_DST_OVERFLOW) -- no byte of any d_outs[f] is written and results[] is left alone:
+ * every byte of the outputs is written by the last kernel (update_batch_splice), which is launched only after the status and
+ * all new sizes have come back.
+ * REPEATED PAIRS follow the single call's rule: each piece of such a row ends up holding the bytes of one of its sources,
+ * whole; which one is unspecified.
+ * ONE GEOMETRY: the touched superblocks of all frames are encoded in one pass, and that pass has one geometry, so all frames of
+ * non-empty arrays must have one superblock size, else STENOS_ERROR_INVALID_PARAMETER.  A store whose frames were made under
+ * one block-size setting (stenos_set_block_size, or none at all: level 1 never shifts) is not affected.
+ * Refused on the host, before any launch that writes, with nothing written: everything stenos_hip_update_rows refuses (the
+ * shape checks on row_bytes, src_stride and n; bytesoftype outside 1..64; an unfinished _async job; ctx's level >= 2,
+ * bytesoftype 1 at level 1, a time limit); m == 0; a NULL in d_frames or d_outs; m, the superblocks of all frames together plus
+ * m, n times the pieces per pair, or any grid above 2^31 - 1; a frame header stenos_hip_decompress refuses (that header's
+ * error code, for the first such frame); frames of different superblock sizes.
+ * PAIRS ARE CHECKED ON THE DEVICE as in stenos_hip_gather_rows_batch (valid: d_frame_ids[i] < m and d_rows[i] < floor(array size
+ * of that frame / row_bytes)); an invalid one gives STENOS_ERROR_INVALID_PARAMETER, in front of any decode error.
+ * d_index has the layout of stenos_hip_frames_index (S + m entries, frame f's slice at entry first[f] + f); NULL has the chains
+ * walked first.  An index that is given is checked per frame as the single call checks it, before anything is written: offsets
+ * must not decrease, every superblock takes at least its 4 header bytes and at most 4 + 2^24 - 1, the last entry of a frame is
+ * at most sizes[f] -- else STENOS_ERROR_INVALID_INPUT / STENOS_ERROR_SRC_OVERFLOW.  It may be the context's own: it is copied
+ * before the context's buffer is written.  No kernel reads outside [d_frames[f], d_frames[f] + sizes[f]), whatever an index
+ * entry or a size field says.
+ * After a successful call the context's index is that of the NEW frames, in the same layout: stenos_hip_last_frames_index
+ * returns it with its length (NULL and 0 when the last call on ctx left no many-frame index: it is valid after
+ * stenos_hip_frames_index and after this call, until the next call that uses the context's index workspace), so the next
+ * stenos_hip_gather_rows_batch or stenos_hip_update_rows_batch on the outputs needs no walk.  stenos_hip_last_index keeps
+ * returning NULL after a batch.
+ * HOW: the heads, the numbering and the walks are those of every call over many frames; the pairs are cut and grouped by
+ * superblock over all frames by the batched gather's kernels; update_batch_plan lists the K touched superblocks of all frames
+ * (a frame's are one run of the list) and tells the host how many each frame has; update_batch_decode decodes them whole, one
+ * wavefront each, into K slots; update_batch_apply copies the pieces' source bytes in; the slots are encoded by the kernels of
+ * stenos_hip_compress_batch, one item without a frame header per touched frame; update_batch_splice_plan makes the new indices
+ * and sizes; update_batch_splice copies every superblock of every frame to its place, one workgroup each.  Host round trips
+ * are three -- the heads, the counts with the status, the new sizes with the status -- and the wait for completion; launches
+ * and round trips depend neither on n nor on the number of superblocks, and on m only through the parallel walks of chains
+ * longer than 256 superblocks and the host paths below; host work and uploaded tables are O(m).
+ * DEVICE MEMORY kept by ctx (S superblocks in all frames, K of them touched): about 0.8 KB per frame (tables), 48 bytes per
+ * superblock + 16 per piece (tables, both indices, the sums); K * superblock size (the slots); K * (superblock size + 4) + one
+ * superblock's worst case per touched frame (the encodings); and the batch encoder's workspace for K superblocks (one padded
+ * slot per block, 16 bytes of tables per block, 21 per superblock): together about 3.2 * K * superblock size, as in the single
+ * call.  The buffers never shrink: they stay at the largest size a call needed until the context is destroyed.
+ * A slot and an encoding take a whole superblock even where the frame is shorter, and the worst-case pad is per touched frame:
+ * 4 096 touched frames of 64 KiB hold 1.75 GiB.
+ * WHO IS SERVED BY WHAT -- MEASURED on MI355X (profiles/update_batch_rate.txt: int32, level 1, index passed in, unique uniform
+ * random pairs, medians of 20; against the only way without this call: the pairs to the host, grouped by frame, one
+ * stenos_hip_update_rows per touched frame, one device copy per untouched frame), batch / baseline in microseconds:
+ *   4 096 frames of 64 KiB, rows of 256 B       256 pairs      801 /  79 026   x98.6
+ *                                            65 536 pairs    1 154 / 799 111   x693     (the condition the call was built under: met)
+ *                                            every row       1 894 / 900 617   x476
+ *   16 frames of 128 MiB, rows of 4 KiB       4 096 pairs    1 453 /   5 469   x3.76
+ *    8 frames of 128 MiB, rows of 4 KiB       4 096 pairs    1 121 /   2 985   x2.66
+ *    1 frame of 1 GiB, rows of 4 KiB          4 096 pairs    1 092 /   1 013   x0.93    (against stenos_hip_update_rows itself)
+ * A store of many frames is served by this call whatever the number of pairs: the baseline pays the single call's fixed cost per
+ * frame touched.  A store that is one large frame stays with stenos_hip_update_rows, which is 7 % faster there.
+ * WHAT IS CHECKED: as in the single call -- touched superblocks are decoded completely, untouched ones are copied, not parsed:
+ * damage in them is NOT detected and arrives in the output.  Touched superblocks with zstd-based codes (the last superblock
+ * under 128 bytes of a level-1 frame; every superblock of a level >= 2 frame) are fetched and inflated on the host, one whole
+ * superblock at a time, which is slow; a touched last superblock under 128 bytes is encoded on the host as well, as the batch
+ * encoder does for its tiny items. */
+STENOS_EXPORT size_t stenos_hip_update_rows_batch(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes,
+						  size_t row_bytes, size_t n, const uint64_t* d_frame_ids, const uint64_t* d_rows, const void* d_src,
+						  size_t src_stride, void* const* d_outs, const size_t* out_sizes, size_t* results, const uint64_t* d_index,
+						  void* stream);
+STENOS_EXPORT const uint64_t* stenos_hip_last_frames_index(stenos_context* ctx, size_t* entries);
+
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),
  * byte delta in four quarter streams above 2048 bytes and its inverse.  src and dst must not overlap.

@@ -97,6 +97,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_gather_rows_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, sz, vp, vp, vp, sz, vp, vp]),
         "stenos_hip_frames_index": (vp, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_update_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, vp]),
+        "stenos_hip_update_rows_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, sz, vp, vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz),
+                                         ctypes.POINTER(sz), vp, vp]),
+        "stenos_hip_last_frames_index": (vp, [vp, ctypes.POINTER(sz)]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
@@ -309,3 +312,43 @@ class Stenos:
         s = src if isinstance(src, int) or src is None else src.data_ptr()
         return self._check(self.lib.stenos_hip_update_rows(self.ctx, frame.data_ptr(), bytesoftype, csize, row_bytes, n, rows.data_ptr() if n else None, s, stride,
                                                            out.data_ptr(), out.numel(), index_ptr, self._stream_ptr()))
+
+    def update_rows_batch(self, frames, bytesoftype: int, csizes, row_bytes: int, frame_ids, rows, src, outs, index_ptr: int | None = None,
+                          src_stride: int | None = None) -> list[int]:
+        """update_rows over many frames in one call: row rows[i] of the ORIGINAL array of frames[frame_ids[i]] is replaced by
+        src[i * src_stride : i * src_stride + row_bytes]; outs[f] receives a complete frame for every listed frame (a byte copy
+        where no pair names it).  frames, outs: lists of uint8 CUDA tensors (frames[f][:csizes[f]]; the same input tensor may be
+        listed twice; an entry of outs may be a (device address, capacity) tuple); frame_ids, rows: as for gather_rows_batch, on
+        the device, ordered on the current stream, as are the source rows.  All frames of non-empty arrays must have one superblock
+        size.  index_ptr: the pointer of frames_index or last_frames_index (None: every chain is walked first); afterwards
+        last_frames_index() is the index of the new frames.  Returns the new sizes.  All or nothing: an invalid pair, a frame that
+        does not fit its output or damage in a touched superblock raises with every output untouched."""
+        import torch
+
+        n = 0 if rows is None else rows.numel()
+        if n:
+            for t, name in ((frame_ids, "frame_ids"), (rows, "rows")):
+                if not t.is_cuda or t.dtype not in (torch.int64, torch.uint64) or not t.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous int64 or uint64 CUDA tensor")
+            if frame_ids.numel() != n:
+                raise ValueError("frame_ids and rows must have the same length")
+        m = len(frames)
+        if len(csizes) != m or len(outs) != m:
+            raise ValueError("frames, csizes and outs must have the same length")
+        P, Z = c_void_p * m, c_size_t * m
+        stride = row_bytes if src_stride is None else src_stride
+        s = src if isinstance(src, int) or src is None else src.data_ptr()
+        optr = [o[0] if isinstance(o, tuple) else o.data_ptr() for o in outs]
+        ocap = [o[1] if isinstance(o, tuple) else o.numel() for o in outs]
+        results = Z(*([0] * m))
+        self._check(self.lib.stenos_hip_update_rows_batch(self.ctx, m, bytesoftype, P(*[t.data_ptr() for t in frames]), Z(*csizes), row_bytes, n,
+                                                               frame_ids.data_ptr() if n else None, rows.data_ptr() if n else None, s, stride, P(*optr), Z(*ocap),
+                                                               results, index_ptr, self._stream_ptr()))
+        return list(results)
+
+    def last_frames_index(self):
+        """(device pointer, entries) of the many-frame index the last frames_index or update_rows_batch on this context left, in
+        the layout of frames_index; (None, 0) when the last call left none."""
+        n = c_size_t(0)
+        p = self.lib.stenos_hip_last_frames_index(self.ctx, ctypes.byref(n))
+        return (p, n.value) if p else (None, 0)

@@ -62,6 +62,7 @@ size_t compress_batch(stenos_context_s* ctx, size_t n, size_t T, const void* con
 	const size_t ntiny = tiny.size();
 	ctx->last_nsb = 0; // (the workspace below holds the batch's superblock offsets from here on)
 	ctx->last_batch = true;
+	ctx->last_frames = 0;
 	// table layout (device and its host mirror): jobs, block and superblock prefix sums, per-item words, tiny list, tiny records
 	const size_t o_jobs = 0, o_bpre = align64(n * sizeof(codec::FrameJob)), o_spre = o_bpre + align64((n + 1) * 8), o_state = o_spre + align64((n + 1) * 8),
 		     o_tiny = o_state + align64(n * sizeof(BatchItemState)), o_tin = o_tiny + align64(ntiny * 4 + 4), o_tout = o_tin + align64(ntiny * sizeof(BatchTinyIn)),

@@ -241,6 +241,7 @@ size_t stenos_private_decompress_block(stenos_context* ctx, const void* src, siz
 		return 0;
 	if (!ctx->device_ready())
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	ctx->last_frames = 0; // (the index workspace takes this superblock's offsets)
 	if (!ctx->in.ensure(4 + csize + 64) || !ctx->out.ensure(dst_size + 64) || !ctx->sboff.ensure(32) || !ctx->misc.ensure(4096))
 		return STENOS_ERROR_ALLOC;
 	const uint64_t index[2] = { 0, 4 + csize };
@@ -499,6 +500,32 @@ size_t stenos_hip_update_rows(stenos_context* ctx, const void* d_frame, size_t b
 	if (!ctx->device_ready())
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return update_rows(ctx, d_frame, bytesoftype, bytes, row_bytes, n, d_rows, d_src, src_stride, d_out, out_size, d_index, (hipStream_t)stream);
+}
+size_t stenos_hip_update_rows_batch(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes, size_t row_bytes, size_t n,
+				    const uint64_t* d_frame_ids, const uint64_t* d_rows, const void* d_src, size_t src_stride, void* const* d_outs, const size_t* out_sizes,
+				    size_t* results, const uint64_t* d_index, void* stream)
+{
+	if (!ctx || !d_frames || !sizes || !d_outs || !out_sizes || !results || (n && (!d_frame_ids || !d_rows || !d_src)))
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: no frame, more frames than one thread each, the shape of the call and what the context
+	// could not compress the touched superblocks with (stenos_hip_update_rows), a NULL among the frames or the outputs
+	if (m == 0 || m > 0x7FFFFFFFull || row_bytes == 0 || src_stride < row_bytes || bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T ||
+	    (n && (n > ~(size_t)0 / row_bytes || n - 1 > (~(size_t)0 - row_bytes) / src_stride)) || needs_strategy(bytesoftype, ctx->level) || ctx->max_nanoseconds)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	for (size_t f = 0; f < m; ++f)
+		if (!d_frames[f] || !d_outs[f])
+			return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return update_rows_batch(ctx, m, bytesoftype, d_frames, sizes, row_bytes, n, d_frame_ids, d_rows, d_src, src_stride, d_outs, out_sizes, results, d_index,
+				 (hipStream_t)stream);
+}
+const uint64_t* stenos_hip_last_frames_index(stenos_context* ctx, size_t* entries)
+{
+	const size_t have = ctx && ctx->last_batch ? ctx->last_frames : 0;
+	if (entries)
+		*entries = have;
+	return have ? ctx->sboff.as<uint64_t>() : nullptr;
 }
 size_t stenos_hip_batch_workspace_bytes(size_t bytesoftype, size_t n, const size_t* bytes)
 {

@@ -263,6 +263,7 @@ size_t enqueue_compress(stenos_context_s* ctx, const uint8_t* d_src, size_t T, s
 	ctx->job_fused_nsb = s_fused;
 	ctx->last_nsb = f.nsb;
 	ctx->last_batch = false;
+	ctx->last_frames = 0;
 	return 0;
 }
 
@@ -286,6 +287,7 @@ size_t compress_device(stenos_context_s* ctx, const void* d_src, size_t T, size_
 	auto host_made = [&](size_t total) { // a frame the host finished: no device-side index, nothing to read back but its size
 		ctx->last_nsb = 0;
 		ctx->last_batch = false;
+		ctx->last_frames = 0;
 		ctx->h_total->total = total;
 		ctx->h_total->encode_status = 0;
 		ctx->set_job(1, stream, !wait, dst_size);

@@ -39,8 +39,10 @@ inline size_t frame_offsets(stenos_context_s* ctx, const void* d_src, size_t siz
 		return 0;
 	if ((!into && !ctx->sboff.ensure((fi.nsb + 2) * 8)) || !ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
 		return STENOS_ERROR_ALLOC;
-	if (!into)
+	if (!into) {
 		into = ctx->sboff.as<uint64_t>();
+		ctx->last_frames = 0; // (the walk overwrites a many-frame index)
+	}
 	*index = into;
 	// (only the test build can set test_serial_walk, stenos_hip_test_walk: one lane walks the chain)
 	if (stenos_k_launch_walk((const uint8_t*)d_src, size, fi.header, fi.nsb, (uint32_t)fi.sb, into, d_status, ctx->test_serial_walk ? nullptr : ctx->walk.p, stream) !=

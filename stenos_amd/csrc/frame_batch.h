@@ -71,14 +71,20 @@ struct FrameBatch { // { ctx, m, d_frames, sizes, stream }: the call's frames, f
 	// takes it: chains up to kBatchSerialWalkMax superblocks do, longer ones take the parallel walk.  A refused frame takes
 	// neither; the frame of an empty array has one entry, its end, which the serial walk writes if walk_empty says so.
 	// d_status: the word a chain that leaves its frame sets DECODE_STATUS_TRUNCATED in, frame f's at d_status + f * status_step.
-	// Returns 0 or STENOS_ERROR_ALLOC; nothing reaches the stream.
-	size_t plan_walks(DecodeArgs* h_args, uint64_t* h_header, uint8_t* h_walk, uint32_t* d_status, size_t status_step, bool walk_empty)
+	// into: a buffer of the caller's with room for S + m offsets, which takes the walks instead (the context's index is left as
+	// it is).  Returns 0 or STENOS_ERROR_ALLOC; nothing reaches the stream.
+	size_t plan_walks(DecodeArgs* h_args, uint64_t* h_header, uint8_t* h_walk, uint32_t* d_status, size_t status_step, bool walk_empty, uint64_t* into = nullptr)
 	{
-		ctx->last_nsb = 0; // (the index workspace holds the batch's superblock offsets from here on)
-		ctx->last_batch = true;
-		if (!ctx->sboff.ensure((S + m + 1) * 8) || !ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
+		if (!into) {
+			ctx->last_nsb = 0; // (the index workspace holds the batch's superblock offsets from here on)
+			ctx->last_batch = true;
+			ctx->last_frames = 0;
+			if (!ctx->sboff.ensure((S + m + 1) * 8))
+				return STENOS_ERROR_ALLOC;
+		}
+		if (!ctx->walk.ensure(stenos_k_walk_scratch_bytes()))
 			return STENOS_ERROR_ALLOC;
-		index = ctx->sboff.as<uint64_t>();
+		index = into ? into : ctx->sboff.as<uint64_t>();
 		for (size_t f = 0; f < m; ++f) {
 			DecodeArgs a = DecodeArgs();
 			a.frame = (const uint8_t*)d_frames[f];
@@ -113,5 +119,63 @@ struct FrameBatch { // { ctx, m, d_frames, sizes, stream }: the call's frames, f
 		return 0;
 	}
 };
+
+// ---- the calls that take (frame number, row number) pairs (gather_batch_host.cpp, update_batch_host.cpp) ----
+// Their frame tables lie at the start of one device buffer of the call's (d) with a page-locked mirror (h):
+//   [frame pointers: m][frame sizes: m] up | [heads: 12 m] down |
+//   [GatherFrame: m][first: m + 1] up, and for the walks [DecodeArgs: m][header sizes: m][walk choice: m] up | o_plan: the call's own
+struct BatchTables {
+	size_t m = 0, o_ptrs = 0, o_sizes = 0, o_heads = 0, o_frames = 0, o_first = 0, o_dargs = 0, o_header = 0, o_walk = 0, o_plan = 0;
+	explicit BatchTables(size_t frames) : m(frames)
+	{
+		o_sizes = o_ptrs + align64(m * 8);
+		o_heads = o_sizes + align64(m * 8);
+		o_frames = o_heads + align64(m * 12);
+		o_first = o_frames + align64(m * sizeof(codec::GatherFrame));
+		o_dargs = o_first + align64((m + 1) * 8);
+		o_header = o_dargs + align64(m * sizeof(DecodeArgs));
+		o_walk = o_header + align64(m * 8);
+		o_plan = o_walk + align64(m);
+	}
+};
+
+// The heads of all frames, their numbering, and the frame table that follows from them, in the mirror.  Returns 0, or the error
+// code of the first frame stenos_hip_decompress refuses, or STENOS_ERROR_INVALID_PARAMETER for more superblocks than one
+// workgroup each allows.
+inline size_t fetch_frames(FrameBatch& b, const BatchTables& t, size_t T, size_t row_bytes, uint8_t* h, uint8_t* d)
+{
+	if (const size_t e = b.fetch_heads(T, h, d, t.o_ptrs, t.o_sizes, t.o_heads, nullptr))
+		return e;
+	b.number();
+	codec::GatherFrame* const frames = (codec::GatherFrame*)(h + t.o_frames);
+	for (size_t f = 0; f < b.m; ++f) {
+		if (b.error[f])
+			return b.error[f];
+		if (b.first[f + 1] > 0x7FFFFFFFull)
+			return STENOS_ERROR_INVALID_PARAMETER;
+		frames[f] = codec::gather_frame((const uint8_t*)b.d_frames[f], b.sizes[f], b.info[f].total, b.info[f].sb, b.info[f].nsb, b.first[f], row_bytes);
+	}
+	memcpy(h + t.o_first, b.first.data(), (b.m + 1) * 8);
+	return 0;
+}
+
+// Every chain is walked on the stream into the context's index (into: a buffer of the caller's instead, plan_walks), in the layout
+// of gather_batch.h (the frame of an empty array has one entry, which the serial walk writes).  A chain that leaves its frame sets
+// DECODE_STATUS_TRUNCATED in *d_status.  The tables from o_frames up to `up_end` (at least o_plan) go up here.  Returns 0,
+// STENOS_ERROR_ALLOC or STENOS_ERROR_UNDEFINED; nothing is waited for.
+inline size_t walk_frames(FrameBatch& b, const BatchTables& t, uint32_t* d_status, uint8_t* h, uint8_t* d, uint64_t* into = nullptr, size_t up_end = 0)
+{
+	DecodeArgs* const h_args = (DecodeArgs*)(h + t.o_dargs);
+	if (const size_t e = b.plan_walks(h_args, (uint64_t*)(h + t.o_header), h + t.o_walk, d_status, 0, true, into))
+		return e;
+	if (hipMemcpyAsync(d + t.o_frames, h + t.o_frames, (up_end > t.o_plan ? up_end : t.o_plan) - t.o_frames, hipMemcpyHostToDevice, b.stream) != hipSuccess)
+		return STENOS_ERROR_UNDEFINED;
+	return b.launch_walks(h_args, (const DecodeArgs*)(d + t.o_dargs), (const uint64_t*)(d + t.o_header), d + t.o_walk);
+}
+
+inline bool batch_shape_refused(stenos_context_s* ctx, size_t m, size_t T)
+{
+	return m == 0 || m > 0x7FFFFFFFull || T == 0 || T > STENOS_K_LDS_MAX_T || (ctx->job_kind && ctx->job_async);
+}
 
 } // namespace stenos_host

@@ -1,76 +1,15 @@
 // gather_batch_host.cpp -- rows of many frames in device memory by (frame number, row number) pairs that live on the device
 // (stenos_hip_gather_rows_batch, stenos_hip_frames_index; gather_batch.h).  Both calls get from the frames' pointers and sizes to
-// a walked index through the front end of the calls that read many frames (FrameBatch, frame_batch.h); the tables, the one
-// status word, the limits and failing on the first refused frame are theirs.
+// a walked index through the front end of the calls that read many frames (FrameBatch, frame_batch.h); the frame tables
+// (BatchTables, fetch_frames, walk_frames), the limits and failing on the first refused frame are those of the calls that take
+// pairs, which stenos_hip_update_rows_batch shares; the one status word is theirs.
+// The tables of both calls lie in one device buffer of their own (gbtab) with a page-locked mirror (h_gbtab), so an index that
+// lives in the context's index buffer survives any number of gather calls.
 #include "frame_batch.h"
 #include "gather_batch.h"
 #include "range_host_codes.h"
 
 namespace stenos_host {
-
-namespace {
-
-// The tables of both calls lie in one device buffer of their own (gbtab) with a page-locked mirror (h_gbtab), so an index that
-// lives in the context's index buffer survives any number of gather calls:
-//   [frame pointers: m][frame sizes: m] up | [heads: 12 m] down |
-//   [GatherFrame: m][first: m + 1] up, and for the walks [DecodeArgs: m][header sizes: m][walk choice: m] up | the PiecePlan (frame_access.h)
-struct BatchTables {
-	size_t m = 0, o_ptrs = 0, o_sizes = 0, o_heads = 0, o_frames = 0, o_first = 0, o_dargs = 0, o_header = 0, o_walk = 0, o_plan = 0;
-	explicit BatchTables(size_t frames) : m(frames)
-	{
-		o_sizes = o_ptrs + align64(m * 8);
-		o_heads = o_sizes + align64(m * 8);
-		o_frames = o_heads + align64(m * 12);
-		o_first = o_frames + align64(m * sizeof(codec::GatherFrame));
-		o_dargs = o_first + align64((m + 1) * 8);
-		o_header = o_dargs + align64(m * sizeof(DecodeArgs));
-		o_walk = o_header + align64(m * 8);
-		o_plan = o_walk + align64(m);
-	}
-};
-
-// The heads of all frames, their numbering, and the frame table that follows from them, in the mirror.  Returns 0, or the error
-// code of the first frame stenos_hip_decompress refuses, or STENOS_ERROR_INVALID_PARAMETER for more superblocks than one
-// workgroup each allows.
-size_t fetch_frames(FrameBatch& b, const BatchTables& t, size_t T, size_t row_bytes)
-{
-	uint8_t* const h = b.ctx->h_gbtab.data();
-	if (const size_t e = b.fetch_heads(T, h, b.ctx->gbtab.as<uint8_t>(), t.o_ptrs, t.o_sizes, t.o_heads, nullptr))
-		return e;
-	b.number();
-	codec::GatherFrame* const frames = (codec::GatherFrame*)(h + t.o_frames);
-	for (size_t f = 0; f < b.m; ++f) {
-		if (b.error[f])
-			return b.error[f];
-		if (b.first[f + 1] > 0x7FFFFFFFull)
-			return STENOS_ERROR_INVALID_PARAMETER;
-		frames[f] = codec::gather_frame((const uint8_t*)b.d_frames[f], b.sizes[f], b.info[f].total, b.info[f].sb, b.info[f].nsb, b.first[f], row_bytes);
-	}
-	memcpy(h + t.o_first, b.first.data(), (b.m + 1) * 8);
-	return 0;
-}
-
-// Every chain is walked on the stream into the context's index, in the layout of gather_batch.h (the frame of an empty array has
-// one entry, which the serial walk writes).  A chain that leaves its frame sets DECODE_STATUS_TRUNCATED in *d_status.  The tables
-// behind o_frames go up here.  Returns 0, STENOS_ERROR_ALLOC or STENOS_ERROR_UNDEFINED; nothing is waited for.
-size_t walk_frames(FrameBatch& b, const BatchTables& t, uint32_t* d_status)
-{
-	uint8_t* const h = b.ctx->h_gbtab.data();
-	uint8_t* const d = b.ctx->gbtab.as<uint8_t>();
-	DecodeArgs* const h_args = (DecodeArgs*)(h + t.o_dargs);
-	if (const size_t e = b.plan_walks(h_args, (uint64_t*)(h + t.o_header), h + t.o_walk, d_status, 0, true))
-		return e;
-	if (hipMemcpyAsync(d + t.o_frames, h + t.o_frames, t.o_plan - t.o_frames, hipMemcpyHostToDevice, b.stream) != hipSuccess)
-		return STENOS_ERROR_UNDEFINED;
-	return b.launch_walks(h_args, (const DecodeArgs*)(d + t.o_dargs), (const uint64_t*)(d + t.o_header), d + t.o_walk);
-}
-
-bool batch_shape_refused(stenos_context_s* ctx, size_t m, size_t T)
-{
-	return m == 0 || m > 0x7FFFFFFFull || T == 0 || T > STENOS_K_LDS_MAX_T || (ctx->job_kind && ctx->job_async);
-}
-
-} // namespace
 
 const uint64_t* frames_index(stenos_context_s* ctx, size_t m, size_t T, const void* const* d_frames, const size_t* sizes, size_t* entries, hipStream_t stream)
 {
@@ -82,18 +21,19 @@ const uint64_t* frames_index(stenos_context_s* ctx, size_t m, size_t T, const vo
 	if (!ctx->gbtab.ensure(t.o_plan + 64) || !ctx->h_gbtab.ensure(t.o_plan + 64))
 		return nullptr;
 	FrameBatch b{ ctx, m, d_frames, sizes, stream };
-	if (fetch_frames(b, t, T, 1))
+	if (fetch_frames(b, t, T, 1, ctx->h_gbtab.data(), ctx->gbtab.as<uint8_t>()))
 		return nullptr;
 	ctx->job_kind = 0;
 	uint32_t* const d_status = (uint32_t*)(ctx->gbtab.as<uint8_t>() + t.o_plan);
 	volatile uint32_t* back = &ctx->h_total->decode_status; // (page-locked)
-	if (hipMemsetAsync(d_status, 0, 4, stream) != hipSuccess || walk_frames(b, t, d_status) ||
+	if (hipMemsetAsync(d_status, 0, 4, stream) != hipSuccess || walk_frames(b, t, d_status, ctx->h_gbtab.data(), ctx->gbtab.as<uint8_t>()) ||
 	    hipMemcpyAsync((void*)back, d_status, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
 		(void)hipStreamSynchronize(stream);
 		return nullptr;
 	}
 	if (*back) // a header or payload runs past the end of its frame
 		return nullptr;
+	ctx->last_frames = (size_t)(b.S + m);
 	if (entries)
 		*entries = (size_t)(b.S + m);
 	return b.index;
@@ -113,7 +53,7 @@ size_t gather_rows_batch(stenos_context_s* ctx, size_t m, size_t T, const void* 
 	if (!ctx->gbtab.ensure(t.o_plan + 64) || !ctx->h_gbtab.ensure(t.o_plan + 64))
 		return STENOS_ERROR_ALLOC;
 	FrameBatch b{ ctx, m, d_frames, sizes, stream };
-	if (const size_t e = fetch_frames(b, t, T, row_bytes))
+	if (const size_t e = fetch_frames(b, t, T, row_bytes, ctx->h_gbtab.data(), ctx->gbtab.as<uint8_t>()))
 		return e;
 	const uint64_t S = b.S;
 	uint8_t* const h = ctx->h_gbtab.data();
@@ -144,7 +84,7 @@ size_t gather_rows_batch(stenos_context_s* ctx, size_t m, size_t T, const void* 
 		if (hipMemcpyAsync(d + t.o_frames, h + t.o_frames, t.o_dargs - t.o_frames, hipMemcpyHostToDevice, stream) != hipSuccess)
 			return fail();
 	}
-	else if (const size_t e = walk_frames(b, t, d_status))
+	else if (const size_t e = walk_frames(b, t, d_status, h, d))
 		return fail(e);
 	else
 		d_index = b.index;

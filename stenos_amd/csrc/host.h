@@ -1,6 +1,6 @@
 // host.h -- internal to the host side of libstenos.so (never installed): the types the units share, the framing helpers
 // and the prototypes they call across.  One unit per concern: host_support.cpp (zstd loader, worker threads),
-// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, host_pointer.cpp and
+// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, host_pointer.cpp and
 // capi.cpp (the exported functions); frame_access.h is the front end of those that read a frame in device memory.  Everything here
 // is hidden from the library's users (libstenos.map).
 #pragma once
@@ -273,6 +273,7 @@ struct stenos_context_s {
 	DevBuf gtab;                                     // gather calls: status word, per-superblock counts, flags and prefixes, the piece table (stenos_hip_gather_rows)
 	DevBuf gbtab;                                    // batched gather calls: frame tables, walk arguments and the piece tables (stenos_hip_gather_rows_batch, stenos_hip_frames_index)
 	DevBuf utab, uraw, uenc;                         // update calls: words, tables and both indices; the touched superblocks decoded; encoded again (stenos_hip_update_rows)
+	DevBuf ubtab;                                    // batched update calls: frame tables, the piece tables, slots' lists, both indices, the encoder's item tables (stenos_hip_update_rows_batch)
 	DevBuf misc;                                     // the words a job's kernels share with the host: DeviceWords, through words()
 	HostBuf h_in, h_out, h_blocks, h_shuf, h_mid0, h_mid1, h_stage, h_tab; // host staging of the strategy layer
 	HostBuf h_btab;                                  // batch calls: page-locked mirror of btab (tables up, per-item results down)
@@ -280,6 +281,7 @@ struct stenos_context_s {
 	HostBuf h_gtab;                                  // gather calls, zstd-based codes only: the row numbers and the superblock flags on the host
 	HostBuf h_gbtab;                                 // batched gather calls: page-locked mirror of gbtab's frame tables
 	HostBuf h_utab;                                  // update calls, zstd-based codes only: the list of touched superblocks and the superblock flags on the host
+	HostBuf h_ubtab;                                 // batched update calls: page-locked mirror of ubtab's tables of O(frames)
 	PinnedWords* h_total = nullptr;                  // what comes back of them (64 page-locked bytes)
 	// last asynchronous job
 	hipStream_t job_stream = nullptr;
@@ -288,6 +290,7 @@ struct stenos_context_s {
 	bool job_host_codes = false; // the last decode met zstd-based superblocks (finished on the host)
 	size_t last_nsb = 0;
 	bool last_batch = false; // the last call that touched the index workspace was a batch: stenos_hip_last_index has no index to give
+	size_t last_frames = 0;  // entries of the many-frame index the context's index workspace holds (stenos_hip_last_frames_index); 0: none
 	bool job_async = false;  // job_kind was set by an _async call (a batch call leaves such a job alone)
 	// optional kernel timing (stenos_hip_set_profiling)
 	bool profiling = false;
@@ -343,7 +346,7 @@ struct stenos_context_s {
 	// everything the context owns on a device: buffers, events and streams
 	void release_device_state()
 	{
-		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc };
+		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc, &ubtab };
 		for (DevBuf* b : all)
 			b->release();
 		if (h_total)
@@ -370,6 +373,7 @@ struct stenos_context_s {
 		set_streams.clear();
 		last_nsb = 0;
 		last_batch = false;
+		last_frames = 0;
 		job_kind = 0;
 	}
 	bool device_ready()
@@ -402,7 +406,7 @@ struct stenos_context_s {
 				free(l);
 			}
 		release_device_state();
-		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab };
+		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab, &h_ubtab };
 		for (HostBuf* b : host)
 			b->release();
 	}
@@ -491,6 +495,11 @@ size_t gather_rows(stenos_context_s* ctx, const void* d_src, size_t T, size_t si
 size_t gather_rows_batch(stenos_context_s* ctx, size_t m, size_t T, const void* const* d_frames, const size_t* sizes, size_t row_bytes, size_t n,
 			 const uint64_t* d_frame_ids, const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, hipStream_t stream);
 const uint64_t* frames_index(stenos_context_s* ctx, size_t m, size_t T, const void* const* d_frames, const size_t* sizes, size_t* entries, hipStream_t stream);
+
+// update_batch_host.cpp
+size_t update_rows_batch(stenos_context_s* ctx, size_t m, size_t T, const void* const* d_frames, const size_t* sizes, size_t row_bytes, size_t n,
+			 const uint64_t* d_frame_ids, const uint64_t* d_rows, const void* d_src, size_t src_stride, void* const* d_outs, const size_t* out_sizes,
+			 size_t* results, const uint64_t* d_index, hipStream_t stream);
 
 // update_host.cpp
 size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t size, size_t row_bytes, size_t n, const uint64_t* d_rows, const void* d_src,

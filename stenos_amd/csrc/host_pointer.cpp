@@ -124,6 +124,7 @@ size_t decompress_chunked(stenos_context_s* ctx, const uint8_t* in, size_t T, co
 	const size_t H = fi.header; // 8, or 12 with a custom superblock size (repeated in every chunk's header)
 	// chunk k on the device: [frame header of its own][its superblocks], 16 bytes further than in the frame per chunk
 	// before it so that the headers do not overlap the neighbours; its index in sboff at entry (s0 - sA) + k
+	ctx->last_frames = 0; // (the index workspace takes the chunks' offsets)
 	if (!chunk_streams(ctx) || !ctx->in.ensure(size + 16 * (chunks + 1) + H + 64) || !ctx->out.ensure((size_t)(oB - oA) + 64) || !ctx->sboff.ensure((count + chunks + 2) * 8))
 		return STENOS_ERROR_ALLOC;
 	std::vector<uint64_t> rel(count + chunks);
@@ -493,6 +494,7 @@ size_t decompress_staged(stenos_context_s* ctx, const void* src, size_t T, size_
 			 void* a_dst)
 {
 	const size_t total = (size_t)fi.total;
+	ctx->last_frames = 0; // (the index workspace takes this frame's offsets)
 	if ((!a_src && !ctx->in.ensure(size + 64)) || (!a_dst && !ctx->out.ensure(total + 64)) || !ctx->sboff.ensure((fi.nsb + 2) * 8))
 		return STENOS_ERROR_ALLOC;
 	if ((!a_src && hipMemcpy(ctx->in.p, src, size, hipMemcpyHostToDevice) != hipSuccess) ||

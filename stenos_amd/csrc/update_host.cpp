@@ -64,6 +64,7 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 	// the context's index takes the new frame's at the end, and the encoder's offsets in between: if it has to grow, the copy
 	// above (whose source it may be) is waited for first
 	const size_t index_bytes = (fi.nsb + 8) * 8;
+	ctx->last_frames = 0; // (a many-frame index in there does not survive this call)
 	if (index_bytes > ctx->sboff.cap && hipStreamSynchronize(stream) != hipSuccess)
 		return STENOS_ERROR_UNDEFINED;
 	if (!ctx->sboff.ensure(index_bytes) || !ctx->misc.ensure(4096))
@@ -180,6 +181,7 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 	ctx->warm = true;
 	ctx->last_nsb = fi.nsb;
 	ctx->last_batch = false;
+	ctx->last_frames = 0;
 	return (size_t)new_total;
 }
 
