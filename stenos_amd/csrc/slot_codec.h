@@ -117,6 +117,32 @@ WV_FN uint32_t lz_distinct_keys_fast(Lds lds, const Layout& L, const U128& e)
 	return first_lane_value(distinct); // the other lanes have not counted
 }
 
+// The same count for the four blocks of a group at once (superblock_codec.h, group4; samples: values 4l and 4l + 1 of lanes
+// 0..19, as lz_distinct_keys_fast<2> takes them).  hash_val's key is a bijection of the value's low byte (an odd multiplier
+// modulo 256), so there are as many distinct keys as distinct low bytes and the low byte indexes the table as it is: no
+// multiplication.  A tag (lane | 32 * round, below 64) fits a byte, so a block's table is 256 bytes and the four tables stand
+// side by side in the KiB at L.tab: all the writes, one wave_sync, all the read-backs, in one divergent region -- where the four
+// calls had two syncs and a region each.  Returns the four counts, a byte each, block 0 lowest.
+WV_FN uint32_t lz_distinct_keys_group4(Lds lds, const Layout& L, const U128& e0, const U128& e1, const U128& e2, const U128& e3)
+{
+	uint32_t distinct = 0; // (lz_precheck_values(4) / 4 = 20 lanes: a tag is lane | 32 * round)
+	lanes_below(lz_precheck_values(4) / 4, [&](const Pred& in) {
+		const U32 lane = lane_id();
+		const U32 v[8] = { e0.x, e0.y, e1.x, e1.y, e2.x, e2.y, e3.x, e3.y };
+		const U32 tag[2] = { lane, lane | 32u };
+		U32 addr[8];
+		for (int k = 0; k < 8; ++k) {
+			addr[k] = U32(L.tab + 256u * (uint32_t)(k >> 1)) + (v[k] & 0xFFu);
+			lds_st8(lds, addr[k], tag[k & 1], in);
+		}
+		wave_sync();
+		for (int k = 0; k < 8; ++k)
+			distinct += (uint32_t)__builtin_popcountll(ballot(in & (lds_ld8(lds, addr[k]) == tag[k & 1]))) << (8 * (k >> 1));
+	});
+	wave_sync();
+	return first_lane_value(distinct); // the other lanes have not counted
+}
+
 // Second rejection test of the mini-LZ for a block of bytesoftype 4 in registers (block_codec.h, lz_try): a value can only
 // match when an equal value precedes it, and equal values have equal hashes.  One bit per 13-bit hash value (1 KiB at
 // L.tab) counts the values whose hash has been seen before; if even with all of them matching the stream exceeds
@@ -513,6 +539,52 @@ WV_FN void slot_rows_emit_rows(Lds lds, const Layout& L, const SlotRows& R, cons
 			wave_sync();
 		}
 	}
+	WV_MARK("emit_end");
+	wave_sync();
+}
+
+// A pass in which every row of every slot is bit-packed against its minimum as a row of VALUES (headers 0..5: no RAW plane, no
+// raw row, no run-length row, no row of differences) -- the upper plane of 12-bit integers, four blocks of it in a group.  The
+// predicates by which slot_rows_emit_rows picks a row's form are then the same in all lanes, and slot_rows_emit_rows_packed
+// writes such a pass in a straight line: nothing is selected between raw and packed operands or between values and
+// differences (R.sd is not read), every lane writes its header and its payload where they belong -- a row of 0 bits ORs zeros --
+// and only a minimum that is not written needs a place outside the image.  Minima that repeat (NORMAL_RLE) are part of it.
+WV_FN bool slot_rows_all_packed(const SlotRows& R)
+{
+	static_assert(PLANE_NORMAL == 2 && PLANE_NORMAL_RLE == 3, "types from PLANE_NORMAL on are the coded ones");
+	return ballot((R.ts >= U32((uint32_t)PLANE_NORMAL << 16)) & (R.hdr() < U32(6u))) == ~0ull;
+}
+// pbase, scr: as for slot_rows_emit_rows; every slot is in use and slot_rows_all_packed(R) holds
+WV_FN void slot_rows_emit_rows_packed(Lds lds, const Layout& L, const SlotRows& R, const U32& pbase, uint32_t scr)
+{
+	const U32 lane = lane_id();
+	const U32 r = lane & 15u;
+	Lds out = lds + L.out;
+	const U32 own = U32(slot2_area(L) + scr - L.out) + lane * 16u;
+	WV_MARK("emit_packed");
+	const U32 bits = R.hdr(); // (:497-503: the header of such a row is its number of bits)
+	{
+		const U32 bitpos = pbase * 8u + r * 4u; // (:768-779)
+		lds_or32_all(out, (bitpos >> 3) & ~3u, bits << (bitpos & 31u));
+	}
+	put_small(out, (pbase + (R.pm >> 16)) * 8u, R.minb() ^ 0x80u, R.emitmin, own);
+	{
+		const Pred isnrle = R.type() == U32(PLANE_NORMAL_RLE); // mins rle mask (:765)
+		if (any(isnrle))
+			put_bits(out, (pbase + 8u) * 8u, row_ballot16(R.eq), isnrle & (r == U32(0u)), own);
+	}
+	// the payload (:562-602): two halves of 8 values, `bits` bytes each, value - minimum on biased bytes
+	const U32 mins = splat_byte0(R.minb());
+	U32 pk[4];
+	for (int k = 0; k < 4; ++k)
+		pk[k] = pack4v(R.sb[k] - mins, bits);
+	const U32 sh4 = bits << 2;
+	U32 s0lo, s0hi, s1lo, s1hi;
+	shl64(pk[1], sh4, s0lo, s0hi);
+	shl64(pk[3], sh4, s1lo, s1hi);
+	const U32 rbase = pbase + (R.pm & 0xFFFFu);
+	lds_put_bytes8(out, rbase, s0lo | pk[0], s0hi);
+	lds_put_bytes8(out, rbase + bits, s1lo | pk[2], s1hi);
 	WV_MARK("emit_end");
 	wave_sync();
 }

@@ -17,6 +17,11 @@ inline uint64_t& emul_group4_count()
 	static uint64_t n = 0;
 	return n;
 }
+inline uint64_t& emul_group4_packed_count() // (groups whose second pass took the straight-line emission of packed rows)
+{
+	static uint64_t n = 0;
+	return n;
+}
 inline uint64_t& emul_group_any_count()
 {
 	static uint64_t n = 0;
@@ -313,13 +318,9 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 				return false;
 			}
 			const uint32_t k0 = (uint32_t)__builtin_ctz(s0.act), k1 = 31u - (uint32_t)__builtin_clz(s0.act);
-			uint32_t keys0 = 0, keys1 = 0, keys2 = 0, keys3 = 0; // (first rejection test of the mini-LZ, as in the pass below)
-			if (T == 4) {
-				keys0 = lz_distinct_keys_fast<2>(lds, M, e0.e);
-				keys1 = lz_distinct_keys_fast<2>(lds, M, e1.e);
-				keys2 = lz_distinct_keys_fast<2>(lds, M, e2.e);
-				keys3 = lz_distinct_keys_fast<2>(lds, M, e3.e);
-			}
+			// (first rejection test of the mini-LZ, as in the pass below; the counts of the four blocks, a byte each)
+			const uint32_t keys = T == 4 ? lz_distinct_keys_group4(lds, M, e0.e, e1.e, e2.e, e3.e) : 0u;
+			const uint32_t keys0 = keys & 0xFFu, keys1 = (keys >> 8) & 0xFFu, keys2 = (keys >> 16) & 0xFFu, keys3 = keys >> 24;
 			// plane k0 of block q -> slot q, plane k1 -> slot 4 + q
 			write_slots_fast(lds, M, e0, T, s0.act, 0, 4);
 			write_slots_fast(lds, M, e1, T, s0.act, 1, 4);
@@ -366,7 +367,16 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 				image_reset_group4(lds, M);
 				const U32 bbase = U32(sink.base()) + incl - bsz;
 				// the second pass first: its rows are in registers; the slots of that pass are the scratch of both emissions
-				slot_rows_emit_rows(lds, M, R, pred_all(true), bbase + U32(hs + k1 - 1u) + (ts0 & 0xFFFFu), 1024, T == 2);
+				// (32-bit elements: a pass of packed rows of values -- 12-bit integers -- has a straight-line form, slot_codec.h)
+				const U32 pbase1 = bbase + U32(hs + k1 - 1u) + (ts0 & 0xFFFFu);
+				if (T == 4 && slot_rows_all_packed(R)) {
+					slot_rows_emit_rows_packed(lds, M, R, pbase1, 1024);
+#ifdef WV_HOST_EMULATION
+					++emul_group4_packed_count();
+#endif
+				}
+				else
+					slot_rows_emit_rows(lds, M, R, pred_all(true), pbase1, 1024, T == 2);
 				group4_emit_heads(lds, M, T, k0, k1, bbase, ts0, R.ts, firstv, 1024);
 				WV_MARK("g4_emit0");
 				slot_rows_reload(lds, M, R, 0, !raw0);
