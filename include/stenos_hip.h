@@ -364,6 +364,81 @@ STENOS_EXPORT size_t stenos_hip_update_rows_batch(stenos_context* ctx, size_t m,
 						  void* stream);
 STENOS_EXPORT const uint64_t* stenos_hip_last_frames_index(stenos_context* ctx, size_t* entries);
 
+/* Append, IN PLACE: the array of a frame in device memory grows by bytes that live in device memory.  d_frame[0 .. bytes) is a
+ * frame of an array A; it lies in a buffer of `capacity` >= bytes bytes; d_src[0 .. src_bytes) are the bytes B.  Afterwards
+ * d_frame holds a frame of A||B and the call returns its size, or an error code.  B may have been written by earlier work on
+ * `stream` (a kernel, a torch op): every enqueued step is ordered on it and the caller need not synchronise.  d_src must not
+ * overlap [d_frame, d_frame + capacity); d_frame and d_src may have any alignment; src_bytes may be any value (not a multiple
+ * of bytesoftype; the array's size need not be one either).  Waits for completion (there is no _async form).  Size the buffer
+ * with stenos_bound(final array size).
+ * THE RESULTING FRAME keeps the frame's own geometry (the shift or custom superblock size of its header, not ctx's block-size
+ * setting).  With sb the superblock size, keep = floor(|A| / sb) and r = |A| mod sb: superblocks 0 .. keep of the frame stay
+ * exactly where and what they are -- the frame of A||B starts with the frame of A up to A's last whole superblock, byte for
+ * byte, because superblocks are encoded independently.  The stream from the header of superblock `keep` on (offset p =
+ * index[keep]: the end of the chain when r == 0) is replaced by the encoding of (last r bytes of A)||B at ctx's level, as
+ * independent superblocks, and the 7-byte size field of the header becomes |A| + src_bytes.  So if the input frame was made by
+ * stenos_hip_compress or stenos_hip_compress_batch at ctx's level into a destination of stenos_bound's size, the result is,
+ * byte for byte and in size, the frame stenos_hip_compress makes of A||B.  For frames of other origin: superblocks 0 .. keep
+ * are unchanged and the new frame decodes to A||B.
+ * WRITES TO d_frame: on success nothing outside the 7 size bytes of the header and [d_frame + p, d_frame + returned size);
+ * nothing at or behind the returned size.  On any failure -- a host-side refusal, a refused index, damage in the last
+ * superblock, a new frame larger than capacity (STENOS_ERROR_DST_OVERFLOW) -- no byte of [d_frame, d_frame + capacity) is
+ * written: every byte goes through the last kernel (append_commit), which is launched only after the status and the new size
+ * have come back.
+ * Refused on the host, before any launch, with nothing written:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        capacity < bytes, bytesoftype outside 1..64, |A| + src_bytes not representable in 56
+ *                                         bits, more than 2^31 - 1 superblocks in the new frame, while an _async job on ctx is
+ *                                         unfinished, and whatever stenos_hip_compress_batch refuses to compress: ctx's level
+ *                                         >= 2, bytesoftype 1 at level 1, a time limit on ctx;
+ *   a frame header stenos_hip_decompress refuses: its error code.
+ * SPECIAL SIZES: src_bytes == 0 returns the end of the chain after the header and index checks and writes nothing.  The frame
+ * of an EMPTY array (|A| == 0) carries no geometry: there the call is stenos_hip_compress of B into [d_frame, d_frame +
+ * capacity) under ctx's level and block-size settings, with THAT call's guarantees (bytes behind the returned size and inside
+ * capacity are scratch, and an overflow may leave the buffer partly written).
+ * d_index: NULL has the chain walked first (stenos_hip_frame_index's walk, whose cost grows with `bytes`).  An index that is
+ * given may be the context's own; the two entries the call uses are checked before anything is written: header size <=
+ * index[keep]; with r > 0, index[keep] + 4 <= index[keep + 1] <= bytes; with r == 0, index[keep] <= bytes -- else
+ * STENOS_ERROR_INVALID_INPUT / STENOS_ERROR_SRC_OVERFLOW.  No kernel reads outside [d_frame, d_frame + bytes) or outside B,
+ * whatever an index entry or a size field says.  After a successful call stenos_hip_last_index returns the index of the NEW
+ * frame (the old entries 0 .. keep followed by the new ones): the next append, gather or update needs no walk.  A pointer
+ * obtained earlier is invalid after the call (after an unsuccessful one too); an index passed in that is the context's own is
+ * copied before the encoder overwrites that buffer.
+ * WHAT IS CHECKED: only the last superblock of A, and only when it is partial (r > 0): it is decoded whole, and damage in it
+ * gives STENOS_ERROR_SRC_OVERFLOW / STENOS_ERROR_INVALID_INPUT as in stenos_hip_decompress.  Everything in front of it is
+ * neither read nor parsed: damage there is NOT detected by this call (with d_index == NULL the walk still sees every superblock
+ * header) and stays in the frame.  A last superblock of A with a zstd-based code (one under 128 bytes of a level-1 frame; any
+ * superblock of a level >= 2 frame, which a level-0/1 context may append to) is fetched and inflated on the host, which is
+ * slow; a NEW last superblock under 128 bytes is coded on the host as the batch encoder does for its tiny items, which costs
+ * one more small round trip.
+ * HOW: append_plan checks the index entries and tells the host p; with r > 0 append_decode decodes superblock keep into a
+ * stitch buffer and one device copy puts the first min(src_bytes, sb - r) bytes of B behind it -- B itself is not staged: the
+ * rest is encoded straight from d_src + (sb - r), and with r == 0 nothing is staged at all; the stitched superblock and the
+ * rest are encoded in ONE pass of the kernels of stenos_hip_compress_batch as two items without a frame header;
+ * append_commit_plan, one thread per new superblock, makes the new index entries and the new size; append_commit copies the
+ * streams behind p, 16 KiB per wavefront, and stores the size field.  Host round trips: the header, p with the status, the new
+ * size with the status, and the wait for completion; launches and round trips depend neither on bytes, src_bytes nor the number
+ * of superblocks.  The fused encoder of stenos_hip_compress does not take streams without a frame header, so large appends run
+ * at the unfused encoder's rate.
+ * DEVICE MEMORY kept by ctx, proportional to the re-encoded bytes r + src_bytes, never to the stored array: one superblock (the
+ * stitch buffer); k * (sb + 4) + one superblock's worst case per stream (the encodings, k new superblocks); the batch
+ * encoder's workspace for k superblocks (one padded slot per block of 256 * bytesoftype bytes, 16 bytes of tables per block, 21
+ * per superblock: together about 3.2 * k * sb); and 8 bytes per superblock of the new frame for the index, twice.  The buffers
+ * never shrink.
+ * WHO IS SERVED BY WHAT -- MEASURED on MI355X (profiles/append_rate.txt, tools/append_rate.py: 1 GiB int32 rand12 frame of 8 192
+ * superblocks, level 1, index passed in, medians of 20; against the only way without this call: stenos_hip_decompress into a scratch
+ * tensor, the new bytes copied behind it, stenos_hip_compress of the concatenation back into the buffer, which leaves the same frame),
+ * append / baseline in microseconds on a superblock boundary (r == 0) and behind half a superblock, device memory held:
+ *     4 KiB      104 /    766  x7.38        186 /    797  x4.28     12 MiB against 1028 MiB
+ *     1 MiB      157 /    747  x4.76        214 /    797  x3.73     16 MiB against 1028 MiB
+ *    64 MiB      222 /    799  x3.61        280 /    844  x3.01     154 MiB against 1090 MiB
+ *     1 GiB    1 517 /  1 527  x1.01      1 574 /  1 578  x1.00     2234 MiB against 2066 MiB
+ * A store that grows by a batch at a time is served by this call: up to 64 MiB it is 3 to 7 times faster and holds a small share
+ * of the memory.  Appending as much as is stored is a tie: the new bytes go through the unfused encoder, the baseline's through the
+ * fused one, which pays for its decode of the old array.  Not measured: the walk (d_index == NULL), other element sizes, level 0. */
+STENOS_EXPORT size_t stenos_hip_append(stenos_context* ctx, void* d_frame, size_t bytesoftype, size_t bytes, size_t capacity, const void* d_src,
+				       size_t src_bytes, const uint64_t* d_index, void* stream);
+
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),
  * byte delta in four quarter streams above 2048 bytes and its inverse.  src and dst must not overlap.

@@ -100,6 +100,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_update_rows_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, sz, vp, vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz),
                                          ctypes.POINTER(sz), vp, vp]),
         "stenos_hip_last_frames_index": (vp, [vp, ctypes.POINTER(sz)]),
+        "stenos_hip_append": (sz, [vp, vp, sz, sz, sz, vp, sz, vp, vp]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
@@ -345,6 +346,16 @@ class Stenos:
                                                                frame_ids.data_ptr() if n else None, rows.data_ptr() if n else None, s, stride, P(*optr), Z(*ocap),
                                                                results, index_ptr, self._stream_ptr()))
         return list(results)
+
+    def append(self, frame, bytesoftype: int, csize: int, src, index_ptr: int | None = None) -> int:
+        """Append IN PLACE: frame[:csize] is the frame of an array A, frame.numel() the capacity of its buffer; afterwards `frame`
+        holds the frame of A followed by the bytes of src, and its size is returned.  frame: a uint8 CUDA tensor; src: a uint8
+        CUDA tensor, or a (device address, length) tuple, that does not overlap it; its bytes may have been written by earlier
+        work on the current stream.  Superblocks in front of A's last whole one stay where and what they are; size the buffer with
+        bound(final array size).  index_ptr: as for gather_rows (it may be last_index()); afterwards last_index() is the index of
+        the new frame.  A frame that does not fit, a refused index or damage in the last superblock raises with `frame` untouched."""
+        s, n = src if isinstance(src, tuple) else (src.data_ptr(), src.numel())
+        return self._check(self.lib.stenos_hip_append(self.ctx, frame.data_ptr(), bytesoftype, csize, frame.numel(), s if n else None, n, index_ptr, self._stream_ptr()))
 
     def last_frames_index(self):
         """(device pointer, entries) of the many-frame index the last frames_index or update_rows_batch on this context left, in

@@ -520,6 +520,20 @@ size_t stenos_hip_update_rows_batch(stenos_context* ctx, size_t m, size_t byteso
 	return update_rows_batch(ctx, m, bytesoftype, d_frames, sizes, row_bytes, n, d_frame_ids, d_rows, d_src, src_stride, d_outs, out_sizes, results, d_index,
 				 (hipStream_t)stream);
 }
+size_t stenos_hip_append(stenos_context* ctx, void* d_frame, size_t bytesoftype, size_t bytes, size_t capacity, const void* d_src, size_t src_bytes,
+			 const uint64_t* d_index, void* stream)
+{
+	if (!ctx || !d_frame || (src_bytes && !d_src))
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: the buffer's shape, a size the header cannot hold, and what the context could not
+	// compress the new superblocks with
+	if (capacity < bytes || bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || (uint64_t)src_bytes >> 56 || needs_strategy(bytesoftype, ctx->level) ||
+	    ctx->level < 0 || ctx->max_nanoseconds)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return append(ctx, d_frame, bytesoftype, bytes, capacity, d_src, src_bytes, d_index, (hipStream_t)stream);
+}
 const uint64_t* stenos_hip_last_frames_index(stenos_context* ctx, size_t* entries)
 {
 	const size_t have = ctx && ctx->last_batch ? ctx->last_frames : 0;

@@ -1,6 +1,6 @@
 // host.h -- internal to the host side of libstenos.so (never installed): the types the units share, the framing helpers
 // and the prototypes they call across.  One unit per concern: host_support.cpp (zstd loader, worker threads),
-// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, host_pointer.cpp and
+// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, append_host.cpp, host_pointer.cpp and
 // capi.cpp (the exported functions); frame_access.h is the front end of those that read a frame in device memory.  Everything here
 // is hidden from the library's users (libstenos.map).
 #pragma once
@@ -274,6 +274,7 @@ struct stenos_context_s {
 	DevBuf gbtab;                                    // batched gather calls: frame tables, walk arguments and the piece tables (stenos_hip_gather_rows_batch, stenos_hip_frames_index)
 	DevBuf utab, uraw, uenc;                         // update calls: words, tables and both indices; the touched superblocks decoded; encoded again (stenos_hip_update_rows)
 	DevBuf ubtab;                                    // batched update calls: frame tables, the piece tables, slots' lists, both indices, the encoder's item tables (stenos_hip_update_rows_batch)
+	DevBuf atab, araw, aenc;                         // append calls: words, the encoder's item tables and the index; the stitched superblock; the new streams (stenos_hip_append)
 	DevBuf misc;                                     // the words a job's kernels share with the host: DeviceWords, through words()
 	HostBuf h_in, h_out, h_blocks, h_shuf, h_mid0, h_mid1, h_stage, h_tab; // host staging of the strategy layer
 	HostBuf h_btab;                                  // batch calls: page-locked mirror of btab (tables up, per-item results down)
@@ -282,6 +283,7 @@ struct stenos_context_s {
 	HostBuf h_gbtab;                                 // batched gather calls: page-locked mirror of gbtab's frame tables
 	HostBuf h_utab;                                  // update calls, zstd-based codes only: the list of touched superblocks and the superblock flags on the host
 	HostBuf h_ubtab;                                 // batched update calls: page-locked mirror of ubtab's tables of O(frames)
+	HostBuf h_atab;                                  // append calls: page-locked mirror of atab's words and item tables
 	PinnedWords* h_total = nullptr;                  // what comes back of them (64 page-locked bytes)
 	// last asynchronous job
 	hipStream_t job_stream = nullptr;
@@ -346,7 +348,7 @@ struct stenos_context_s {
 	// everything the context owns on a device: buffers, events and streams
 	void release_device_state()
 	{
-		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc, &ubtab };
+		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc, &ubtab, &atab, &araw, &aenc };
 		for (DevBuf* b : all)
 			b->release();
 		if (h_total)
@@ -406,7 +408,7 @@ struct stenos_context_s {
 				free(l);
 			}
 		release_device_state();
-		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab, &h_ubtab };
+		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab, &h_ubtab, &h_atab };
 		for (HostBuf* b : host)
 			b->release();
 	}
@@ -504,6 +506,10 @@ size_t update_rows_batch(stenos_context_s* ctx, size_t m, size_t T, const void* 
 // update_host.cpp
 size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t size, size_t row_bytes, size_t n, const uint64_t* d_rows, const void* d_src,
 		   size_t src_stride, void* d_out, size_t out_size, const uint64_t* d_index, hipStream_t stream);
+
+// append_host.cpp
+size_t append(stenos_context_s* ctx, void* d_frame, size_t T, size_t size, size_t capacity, const void* d_src, size_t src_bytes, const uint64_t* d_index,
+	      hipStream_t stream);
 
 // host_pointer.cpp
 size_t compress_host(stenos_context_s* ctx, const void* src, size_t T, size_t bytes, void* dst, size_t dst_size);
