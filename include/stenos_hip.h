@@ -439,6 +439,84 @@ STENOS_EXPORT const uint64_t* stenos_hip_last_frames_index(stenos_context* ctx, 
 STENOS_EXPORT size_t stenos_hip_append(stenos_context* ctx, void* d_frame, size_t bytesoftype, size_t bytes, size_t capacity, const void* d_src,
 				       size_t src_bytes, const uint64_t* d_index, void* stream);
 
+/* stenos_hip_append over many frames in one call, IN PLACE: all arrays are host arrays of m.  Frame f is d_frames[f][0 ..
+ * sizes[f]), the frame of an array A_f, in a buffer of capacities[f] >= sizes[f] bytes; d_srcs[f][0 .. src_sizes[f]) are the bytes
+ * B_f, in device memory; they may have been written by earlier work on `stream`.  Afterwards d_frames[f] holds a frame of
+ * A_f||B_f, for every f.  Returns 0 when the call ran, with results[f] the new frame sizes, or one error code for the whole
+ * call.  Waits for completion (there is no _async form).  The contract is stenos_hip_append's, frame by frame: every frame ends
+ * up holding, byte for byte and in size, what stenos_hip_append alone would leave for it -- for frames made by
+ * stenos_hip_compress or stenos_hip_compress_batch at ctx's level into destinations of stenos_bound's size, the frame
+ * stenos_hip_compress makes of A_f||B_f.  Each frame keeps its own header geometry; superblocks 0 .. keep_f of a frame are
+ * never read or written.  Only what follows is new.
+ * WRITES TO d_frames: all or nothing.  On success nothing outside each frame's 7 size bytes and [d_frames[f] + p_f, d_frames[f] +
+ * results[f]).  On any error -- a host-side refusal, a refused index entry of any frame, damage in any partial last superblock,
+ * any new frame larger than its capacity (STENOS_ERROR_DST_OVERFLOW) -- no byte of any buffer is written and results[] is left
+ * alone: every byte of every frame goes through the last kernel (append_batch_commit), which is launched only after the status
+ * and all new sizes have come back.  There is no per-frame partial success.
+ * src_sizes[f] == 0: the frame is checked (its header, its two index entries) and not written; results[f] is the end of its
+ * chain.  If all sources are empty, nothing is written anywhere.
+ * The frame of an EMPTY array (|A_f| == 0) is how a page starts.  It carries no geometry: with src_sizes[f] > 0 its bytes are
+ * encoded with a frame header under ctx's level and block-size setting, and the result is byte for byte what
+ * stenos_hip_compress makes of B_f.  It goes through the same staging and the same last kernel, so all-or-nothing holds for
+ * it too -- which is more than stenos_hip_append gives, which hands such a frame to stenos_hip_compress.
+ * ONE GEOMETRY: the new superblocks of all frames are encoded in one pass, and that pass has one geometry, so all frames of
+ * non-empty arrays must have one superblock size, and the size ctx would give the empty ones must equal it, else
+ * STENOS_ERROR_INVALID_PARAMETER.  A store whose frames were made under one block-size setting (stenos_set_block_size, or none at
+ * all: level 1 never shifts) is not affected.
+ * Refused on the host, before any launch that writes, with nothing written: everything stenos_hip_append refuses, of any frame
+ * (capacities[f] < sizes[f]; a size the 56-bit field cannot hold; bytesoftype outside 1..64; an unfinished _async job; ctx's
+ * level >= 2, bytesoftype 1 at level 1, a time limit); m == 0 or above 2^31 - 1; a NULL in d_frames; a NULL source with a
+ * non-zero size; a frame header stenos_hip_decompress refuses (that header's error code, for the first such frame); the old or
+ * the new superblocks of all frames together plus m, or any grid, above 2^31 - 1; frames of different superblock sizes; two
+ * frame buffers [d_frames[f], + capacities[f]) that overlap, or a source that overlaps a frame buffer (the host sorts the 2 m
+ * intervals; the in-place commit would race with itself) -- STENOS_ERROR_INVALID_PARAMETER.  Sources may overlap each other.
+ * d_index has the layout of stenos_hip_frames_index (S + m entries, frame f's slice at entry first[f] + f); NULL has the chains
+ * walked first.  It may be the context's own (stenos_hip_last_frames_index): it is copied before the encoder overwrites that
+ * buffer.  Per frame only the two entries stenos_hip_append uses are checked, by the same comparisons without sums, before
+ * anything is written.  No kernel reads outside [d_frames[f], d_frames[f] + sizes[f]) or outside B_f, whatever an entry says.
+ * After a successful call the context's index is that of the NEW frames, in the same layout: stenos_hip_last_frames_index
+ * returns it, so a following stenos_hip_gather_rows_batch, stenos_hip_update_rows_batch or stenos_hip_append_batch walks
+ * nothing.  After a failure stenos_hip_last_frames_index returns NULL and 0.  stenos_hip_last_index returns NULL, as after any
+ * batch.
+ * WHAT IS CHECKED: as in the single call -- of every frame only the last superblock of A_f, and only when it is partial: it is
+ * decoded whole.  Everything in front of it is neither read nor parsed: damage there is NOT detected by this call and stays in
+ * the frame.  A partial last superblock with a zstd-based code (one under 128 bytes of a level-1 frame; any superblock of a
+ * level >= 2 frame) is fetched and inflated on the host, one frame at a time, which is slow; NEW last superblocks under 128
+ * bytes are coded on the host as the batch encoder does for its tiny items, with one more round trip for all of them together.
+ * HOW: the heads, the numbering and the walks are those of every call over many frames; append_batch_plan, one thread per
+ * frame, runs the single call's entry checks and publishes p_f; append_batch_decode, one wavefront per frame with a partial last
+ * superblock, decodes it into the frame's stitch slot of r_f + n0_f bytes (n0_f = min(src_sizes[f], sb - r_f): not a whole
+ * superblock per frame); append_batch_stitch copies the first n0_f bytes of every B_f behind them; one pass of the kernels of
+ * stenos_hip_compress_batch encodes up to 2 m items -- the stitched superblock of a frame, then the rest of B_f read where the
+ * caller has it, both without a frame header; append_batch_commit_plan, one thread per new superblock, writes the new index
+ * entries and checks every encoder length; append_batch_index moves the old entries 0 .. keep_f to the new layout;
+ * append_batch_commit cuts the streams of all items into 16 KiB chunks, one per wavefront, and stores the size fields.  Host
+ * round trips are three -- the heads, the status with the flags, the new sizes with the status -- and the wait for completion;
+ * launches and round trips depend neither on the bytes nor on the superblocks, and on m only through the parallel walks of
+ * chains longer than 256 superblocks and the host zstd paths: there is no copy and no launch per frame.
+ * DEVICE MEMORY kept by ctx (S old, S' new superblocks in all frames; k_i new superblocks in item i of up to 2 m): about 1.3 KB
+ * per frame (tables); 8 (S + m) + 8 (S' + m) (both indices); r_f + n0_f per frame, rounded up to 64 (the stitch slots); k_i *
+ * (sb + 4) + one superblock's worst case PER ITEM (the encodings: every item is kept roomy, because the encoder's capacity
+ * rules would change output bytes); and the batch encoder's workspace for all new superblocks (about 3.2 * sb each).  The
+ * buffers never shrink.  Measured: 4 096 int32 frames of 64 KiB with 256 bytes appended to each hold 1 624 MiB, 0.40 MiB per frame,
+ * of which the roomy room is 0.26 MiB per item; shrinking it is left for later.
+ * WHO IS SERVED BY WHAT -- MEASURED on MI355X (profiles/append_batch_rate.txt, tools/append_batch_rate.py: int32 rand12, level 1,
+ * index passed in, medians of 20; against the only way without this call: a loop of stenos_hip_append, one call per frame, each
+ * given its frame's slice of a caller-held frames index -- which leaves the context with the index of the last frame only),
+ * batch / baseline in microseconds, device memory held:
+ *   4 096 frames of 64 KiB   256 B to every frame     1 370 / 736 730   x538     1 624 MiB against 2 MiB
+ *                            4 KiB to every frame     1 340 / 739 773   x552     30 MiB more
+ *                            256 B to every 16th        653 /  45 779   x70.1
+ *   8 frames of 128 MiB      1 MiB each                 177 /   1 206   x6.81    20 MiB against 2 MiB
+ *   1 frame of 1 GiB         4 KiB                      127 /     101   x0.79    (against stenos_hip_append itself)
+ *                            64 MiB                     240 /     224   x0.93    140 MiB against 66 MiB
+ * A store of many frames is served by this call: the loop pays the single call's fixed cost per frame, and leaves the context with
+ * the index of the last frame only.  A store that is one frame stays with stenos_hip_append: there this call LOSES, by 21 % for
+ * 4 KiB and by 7 % for 64 MiB.  Not measured: the walks (d_index == NULL), other element sizes, level 0. */
+STENOS_EXPORT size_t stenos_hip_append_batch(stenos_context* ctx, size_t m, size_t bytesoftype, void* const* d_frames, const size_t* sizes,
+					     const size_t* capacities, const void* const* d_srcs, const size_t* src_sizes, size_t* results,
+					     const uint64_t* d_index, void* stream);
+
 /* Whole-buffer byte kernels of the path on device memory (reference stenos/internal/shuffle.h:33,45 and
  * delta.h:34,39): byte transpose of `bytes / bytesoftype` elements and its inverse (leftover bytes copied),
  * byte delta in four quarter streams above 2048 bytes and its inverse.  src and dst must not overlap.

@@ -101,6 +101,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                          ctypes.POINTER(sz), vp, vp]),
         "stenos_hip_last_frames_index": (vp, [vp, ctypes.POINTER(sz)]),
         "stenos_hip_append": (sz, [vp, vp, sz, sz, sz, vp, sz, vp, vp]),
+        "stenos_hip_append_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz),
+                                    ctypes.POINTER(sz), vp, vp]),
         "stenos_hip_batch_workspace_bytes": (sz, [sz, sz, ctypes.POINTER(sz)]),
         "stenos_hip_set_profiling": (None, [vp, c_int]),
         "stenos_hip_kernel_ms": (ctypes.c_double, [vp, c_int]),
@@ -357,9 +359,30 @@ class Stenos:
         s, n = src if isinstance(src, tuple) else (src.data_ptr(), src.numel())
         return self._check(self.lib.stenos_hip_append(self.ctx, frame.data_ptr(), bytesoftype, csize, frame.numel(), s if n else None, n, index_ptr, self._stream_ptr()))
 
+    def append_batch(self, frames, bytesoftype: int, csizes, srcs, index_ptr: int | None = None) -> list[int]:
+        """append over many frames in one call, IN PLACE: frames[f][:csizes[f]] is the frame of an array A_f; afterwards frames[f]
+        holds the frame of A_f followed by the bytes of srcs[f].  frames: uint8 CUDA tensors (the capacity of a buffer is its
+        numel()) or (device address, capacity) tuples; srcs: uint8 CUDA tensors, (device address, length) tuples, or None for
+        nothing; their bytes may have been written by earlier work on the current stream.  No two buffers may overlap, and no
+        source may overlap a buffer.  All frames of non-empty arrays must have one superblock size.  index_ptr: the pointer of
+        frames_index or last_frames_index (None: every chain is walked first); afterwards last_frames_index() is the index of the
+        new frames.  Returns the new sizes.  All or nothing: a frame that does not fit its buffer, a refused index entry or damage
+        in a partial last superblock of any frame raises StenosError with every buffer untouched."""
+        m = len(frames)
+        if len(csizes) != m or len(srcs) != m:
+            raise ValueError("frames, csizes and srcs must have the same length")
+        P, Z = c_void_p * m, c_size_t * m
+        fptr = [t[0] if isinstance(t, tuple) else t.data_ptr() for t in frames]
+        fcap = [t[1] if isinstance(t, tuple) else t.numel() for t in frames]
+        pairs = [(None, 0) if s is None else s if isinstance(s, tuple) else (s.data_ptr(), s.numel()) for s in srcs]
+        results = Z(*([0] * m))
+        self._check(self.lib.stenos_hip_append_batch(self.ctx, m, bytesoftype, P(*fptr), Z(*csizes), Z(*fcap), P(*[p if n else None for p, n in pairs]),
+                                                     Z(*[n for _, n in pairs]), results, index_ptr, self._stream_ptr()))
+        return list(results)
+
     def last_frames_index(self):
-        """(device pointer, entries) of the many-frame index the last frames_index or update_rows_batch on this context left, in
-        the layout of frames_index; (None, 0) when the last call left none."""
+        """(device pointer, entries) of the many-frame index the last frames_index, update_rows_batch or append_batch on this
+        context left, in the layout of frames_index; (None, 0) when the last call left none."""
         n = c_size_t(0)
         p = self.lib.stenos_hip_last_frames_index(self.ctx, ctypes.byref(n))
         return (p, n.value) if p else (None, 0)

@@ -92,7 +92,9 @@ UPD_FN void append_plan_thread(const AppendArgs& a)
 // already, so every thread finds its own place.  Every length is checked as update_new_length checks the encoder's (a
 // superblock has its header at least, and at most the payload a header can announce; a stream's offsets start at 0), the
 // last thread publishes both streams' bytes and the new total.  Returns UPDATE_ST_* bits.
-UPD_FN uint32_t append_commit_plan_thread(const AppendArgs& a, uint32_t j)
+// (start: where the offsets of the first stream that has superblocks start -- 0 for a stream without a frame header, which is
+// all stenos_hip_append has; the many-frame call hands in a stream with one, append_batch_codec.h)
+UPD_FN uint32_t append_commit_plan_at(const AppendArgs& a, uint32_t j, uint64_t start)
 {
 	if (j >= a.k)
 		return 0;
@@ -104,7 +106,7 @@ UPD_FN uint32_t append_commit_plan_thread(const AppendArgs& a, uint32_t j)
 	uint32_t st = 0;
 	if (e1 < e0 || e1 - e0 < 4 || e1 - e0 > UPDATE_MAX_SB_FRAME_BYTES) // (the encoder writes no such offsets)
 		st = UPDATE_ST_INVALID;
-	if ((j == 0 || j == a.k0) && e0 != 0)
+	if ((j == 0 || j == a.k0) && e0 != (j == 0 ? start : 0))
 		st = UPDATE_ST_INVALID;
 	const uint64_t base = p + (second ? len0 : 0);
 	upd_st64(a.idx + a.keep + j, base + e0);
@@ -116,6 +118,7 @@ UPD_FN uint32_t append_commit_plan_thread(const AppendArgs& a, uint32_t j)
 	}
 	return st;
 }
+UPD_FN uint32_t append_commit_plan_thread(const AppendArgs& a, uint32_t j) { return append_commit_plan_at(a, j, 0); }
 
 // ---- append_commit: wavefront g of the grid, the only writer to the frame ----
 // The two streams are cut into chunks of APPEND_COMMIT_CHUNK bytes, the first stream's first; wavefront g copies chunk g to

@@ -534,6 +534,28 @@ size_t stenos_hip_append(stenos_context* ctx, void* d_frame, size_t bytesoftype,
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return append(ctx, d_frame, bytesoftype, bytes, capacity, d_src, src_bytes, d_index, (hipStream_t)stream);
 }
+size_t stenos_hip_append_batch(stenos_context* ctx, size_t m, size_t bytesoftype, void* const* d_frames, const size_t* sizes, const size_t* capacities,
+			       const void* const* d_srcs, const size_t* src_sizes, size_t* results, const uint64_t* d_index, void* stream)
+{
+	if (!ctx)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	ctx->last_frames = 0; // (a call that fails leaves no many-frame index)
+	if (!d_frames || !sizes || !capacities || !d_srcs || !src_sizes || !results)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: no frame, more frames than one thread each, what stenos_hip_append refuses of every frame
+	// (the buffer's shape, a size the header cannot hold, a NULL), and what the context could not compress the new superblocks with
+	if (m == 0 || m > 0x7FFFFFFFull || bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || needs_strategy(bytesoftype, ctx->level) || ctx->level < 0 ||
+	    ctx->max_nanoseconds)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	for (size_t f = 0; f < m; ++f)
+		if (!d_frames[f] || capacities[f] < sizes[f] || (uint64_t)src_sizes[f] >> 56 || (src_sizes[f] && !d_srcs[f]))
+			return STENOS_ERROR_INVALID_PARAMETER;
+	if (append_batch_overlap(m, d_frames, capacities, d_srcs, src_sizes))
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return append_batch(ctx, m, bytesoftype, d_frames, sizes, capacities, d_srcs, src_sizes, results, d_index, (hipStream_t)stream);
+}
 const uint64_t* stenos_hip_last_frames_index(stenos_context* ctx, size_t* entries)
 {
 	const size_t have = ctx && ctx->last_batch ? ctx->last_frames : 0;

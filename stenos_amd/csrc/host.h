@@ -1,6 +1,6 @@
 // host.h -- internal to the host side of libstenos.so (never installed): the types the units share, the framing helpers
 // and the prototypes they call across.  One unit per concern: host_support.cpp (zstd loader, worker threads),
-// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, append_host.cpp, host_pointer.cpp and
+// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, append_host.cpp, append_batch_host.cpp, host_pointer.cpp and
 // capi.cpp (the exported functions); frame_access.h is the front end of those that read a frame in device memory.  Everything here
 // is hidden from the library's users (libstenos.map).
 #pragma once
@@ -275,6 +275,7 @@ struct stenos_context_s {
 	DevBuf utab, uraw, uenc;                         // update calls: words, tables and both indices; the touched superblocks decoded; encoded again (stenos_hip_update_rows)
 	DevBuf ubtab;                                    // batched update calls: frame tables, the piece tables, slots' lists, both indices, the encoder's item tables (stenos_hip_update_rows_batch)
 	DevBuf atab, araw, aenc;                         // append calls: words, the encoder's item tables and the index; the stitched superblock; the new streams (stenos_hip_append)
+	DevBuf abtab, abraw, abenc;                      // batched append calls: frame tables, the encoder's item tables, words and both indices; the stitch slots; the new streams (stenos_hip_append_batch)
 	DevBuf misc;                                     // the words a job's kernels share with the host: DeviceWords, through words()
 	HostBuf h_in, h_out, h_blocks, h_shuf, h_mid0, h_mid1, h_stage, h_tab; // host staging of the strategy layer
 	HostBuf h_btab;                                  // batch calls: page-locked mirror of btab (tables up, per-item results down)
@@ -284,6 +285,7 @@ struct stenos_context_s {
 	HostBuf h_utab;                                  // update calls, zstd-based codes only: the list of touched superblocks and the superblock flags on the host
 	HostBuf h_ubtab;                                 // batched update calls: page-locked mirror of ubtab's tables of O(frames)
 	HostBuf h_atab;                                  // append calls: page-locked mirror of atab's words and item tables
+	HostBuf h_abtab;                                 // batched append calls: page-locked mirror of abtab's tables of O(frames)
 	PinnedWords* h_total = nullptr;                  // what comes back of them (64 page-locked bytes)
 	// last asynchronous job
 	hipStream_t job_stream = nullptr;
@@ -348,7 +350,7 @@ struct stenos_context_s {
 	// everything the context owns on a device: buffers, events and streams
 	void release_device_state()
 	{
-		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc, &ubtab, &atab, &araw, &aenc };
+		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc, &ubtab, &atab, &araw, &aenc, &abtab, &abraw, &abenc };
 		for (DevBuf* b : all)
 			b->release();
 		if (h_total)
@@ -408,7 +410,7 @@ struct stenos_context_s {
 				free(l);
 			}
 		release_device_state();
-		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab, &h_ubtab, &h_atab };
+		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab, &h_ubtab, &h_atab, &h_abtab };
 		for (HostBuf* b : host)
 			b->release();
 	}
@@ -510,6 +512,11 @@ size_t update_rows(stenos_context_s* ctx, const void* d_frame, size_t T, size_t 
 // append_host.cpp
 size_t append(stenos_context_s* ctx, void* d_frame, size_t T, size_t size, size_t capacity, const void* d_src, size_t src_bytes, const uint64_t* d_index,
 	      hipStream_t stream);
+
+// append_batch_host.cpp
+bool append_batch_overlap(size_t m, void* const* d_frames, const size_t* capacities, const void* const* d_srcs, const size_t* src_sizes);
+size_t append_batch(stenos_context_s* ctx, size_t m, size_t T, void* const* d_frames, const size_t* sizes, const size_t* capacities, const void* const* d_srcs,
+		    const size_t* src_sizes, size_t* results, const uint64_t* d_index, hipStream_t stream);
 
 // host_pointer.cpp
 size_t compress_host(stenos_context_s* ctx, const void* src, size_t T, size_t bytes, void* dst, size_t dst_size);
