@@ -731,6 +731,14 @@ WV_HD bool lz_precheck_passes(uint32_t T, uint32_t distinct, uint32_t max_size)
 	// (Its other test, lower > max_size (:221-223), is implied: it would make 5 * lower > 5 * max_size.)
 	return !(5 * lower > 2 * max_size);
 }
+// The same test on values that differ from lane to lane (superblock_codec.h, group4: the lanes of a block hold its count and its
+// size): the same integers, so the same decisions.  lower = nq / 8 + nq * B - (nq - distinct) * (B - 1), the constant part first.
+WV_FN Pred lz_precheck_passes_lanes(uint32_t T, const U32& distinct, const U32& max_size)
+{
+	const uint32_t B = lz_width(T), nq = lz_precheck_values(T);
+	const U32 lower = distinct * U32(B - 1) + U32(nq / 8 + nq * B - nq * (B - 1));
+	return !(lower * U32(5u) > max_size * U32(2u));
+}
 // distinct hash keys among the first nq values of the block at L.in; uses the first KiB of the image (not L.lz)
 WV_FN uint32_t lz_distinct_keys(Lds lds, const Layout& L, uint32_t T)
 {

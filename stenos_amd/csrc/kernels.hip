@@ -192,7 +192,7 @@ __device__ __forceinline__ void encode_superblocks_body(FrameJob j, uint64_t nsb
 	bool prev_spec = false;       // ... and its raw bytes were put where a copy behind copies goes
 	uint32_t prev_run[FUSED_WAVES];
 	bool guess_copy = false; // the workgroup's last superblock ended up as a copy
-	bool group_hint = true;  // the wave's last blocks had the shape that groups of four blocks want (superblock_codec.h)
+	uint32_t group_hint = StreamSink::GROUP_TRY; // whether the wave's last blocks had the shape that groups of four blocks want, and their planes (superblock_codec.h)
 	uint32_t ncopies = 0;    // superblocks this workgroup stored as copies
 	if (threadIdx.x == 0)
 		shared[2] = 0;

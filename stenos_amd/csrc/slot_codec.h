@@ -54,6 +54,32 @@ WV_FN SameScan scan_same_fast(const RawBlock& b, uint32_t T)
 	return s;
 }
 
+// The scan of four blocks of 32-bit elements against the planes the wave expects to vary (superblock_codec.h, group4: the planes
+// of its last group).  want: 0xFF in the bytes of the two expected planes.  True: in each of the four blocks exactly these two
+// planes are not constant -- what scan_same_fast says with act = the two planes for every block, exactly: each of the two planes
+// varies in each block (eight tests "some lane", a vector compare and a branch each, where the sixteen ballots of four general
+// scans are turned into bits, ORed and compared in the scalar unit), and no other plane varies in any block (one test over the OR
+// of the four).  False: something else holds; nothing is decided, the caller scans as if there had been no expectation.
+WV_FN bool scan_expected_group4(const U128& e0, const U128& e1, const U128& e2, const U128& e3, uint32_t want)
+{
+	const uint32_t lowbit = want & (0u - want);
+	const uint32_t m0 = lowbit * 0xFFu, m1 = want ^ m0; // the lower and the upper of the two planes
+	const U128* const e[4] = { &e0, &e1, &e2, &e3 };
+	U32 all(0u);
+	for (int q = 0; q < 4; ++q) {
+		const U32 f(readlane(e[q]->x, 0));
+		const U32 x = ((e[q]->x ^ f) | (e[q]->y ^ f)) | ((e[q]->z ^ f) | (e[q]->w ^ f));
+		if (!any((x & U32(m0)) != U32(0u)))
+			return false;
+		if (!any((x & U32(m1)) != U32(0u)))
+			return false;
+		all = all | x;
+	}
+	return !any((all & U32(~want)) != U32(0u));
+}
+// act (two planes) as the byte mask scan_expected_group4 takes
+WV_HD uint32_t plane_bytes(uint32_t act) { return ((act * 0x00204081u) & 0x01010101u) * 0xFFu; }
+
 // step: distance between the slots of consecutive planes (1: side by side; 4: a group of four blocks keeps the slots of one
 // plane of its blocks side by side, superblock_codec.h)
 WV_FN void write_slots_fast(Lds lds, const Layout& L, const RawBlock& b, uint32_t T, uint32_t act, uint32_t slot, uint32_t step = 1)
@@ -88,6 +114,35 @@ WV_FN void write_slots_fast(Lds lds, const Layout& L, const RawBlock& b, uint32_
 		}
 		if (act & 8u)
 			lds_st32(lds, a + slot * SLOT2_BYTES, perm_bytes(t3, t1, 0x07060302u), pred_all(true));
+	}
+}
+
+// The same for the four blocks of a group of 32-bit elements, whose planes k0 < k1 are the ones that vary in every block: plane k0
+// of block q -> slot q, plane k1 -> slot 4 + q (write_slots_fast with step 4, four times, decides on act once per block: four times
+// the same answer).  The byte selectors of the two transpose steps are wave-uniform values picked once; the planes share the
+// first step when they lie in the same half of the element.
+WV_FN void write_slots_group4(Lds lds, const Layout& L, const U128& e0, const U128& e1, const U128& e2, const U128& e3, uint32_t k0, uint32_t k1)
+{
+	const U32 a = U32(slot2_area(L)) + lane_id() * 4u;
+	const U128* const e[4] = { &e0, &e1, &e2, &e3 };
+	const uint32_t LOW = 0x05010400u, HIGH = 0x07030602u; // bytes 0 and 1 / 2 and 3 of two elements each
+	const uint32_t EVEN = 0x05040100u, ODD = 0x07060302u; // the lower / the upper plane of such a pair
+	const U32 q0((k0 & 1u) ? ODD : EVEN), q1((k1 & 1u) ? ODD : EVEN);
+	if ((k0 ^ k1) < 2u) { // (both in one half)
+		const U32 h((k0 & 2u) ? HIGH : LOW);
+		for (uint32_t q = 0; q < 4; ++q) {
+			const U32 t = perm_bytes_v(e[q]->y, e[q]->x, h), u = perm_bytes_v(e[q]->w, e[q]->z, h);
+			lds_st32(lds, a + q * SLOT2_BYTES, perm_bytes_v(u, t, q0), pred_all(true));
+			lds_st32(lds, a + (4 + q) * SLOT2_BYTES, perm_bytes_v(u, t, q1), pred_all(true));
+		}
+		return;
+	}
+	// k0 in the lower half, k1 in the upper
+	for (uint32_t q = 0; q < 4; ++q) {
+		const U32 t0 = perm_bytes(e[q]->y, e[q]->x, LOW), t2 = perm_bytes(e[q]->w, e[q]->z, LOW);
+		lds_st32(lds, a + q * SLOT2_BYTES, perm_bytes_v(t2, t0, q0), pred_all(true));
+		const U32 t1 = perm_bytes(e[q]->y, e[q]->x, HIGH), t3 = perm_bytes(e[q]->w, e[q]->z, HIGH);
+		lds_st32(lds, a + (4 + q) * SLOT2_BYTES, perm_bytes_v(t3, t1, q1), pred_all(true));
 	}
 }
 
@@ -136,8 +191,10 @@ WV_FN uint32_t lz_distinct_keys_group4(Lds lds, const Layout& L, const U128& e0,
 			lds_st8(lds, addr[k], tag[k & 1], in);
 		}
 		wave_sync();
-		for (int k = 0; k < 8; ++k)
-			distinct += (uint32_t)__builtin_popcountll(ballot(in & (lds_ld8(lds, addr[k]) == tag[k & 1]))) << (8 * (k >> 1));
+		for (int q = 0; q < 4; ++q) { // (the two counts of a block are added before they are shifted into the block's byte)
+			const uint64_t m0 = ballot(in & (lds_ld8(lds, addr[2 * q]) == tag[0])), m1 = ballot(in & (lds_ld8(lds, addr[2 * q + 1]) == tag[1]));
+			distinct |= (uint32_t)(__builtin_popcountll(m0) + __builtin_popcountll(m1)) << (8 * q);
+		}
 	});
 	wave_sync();
 	return first_lane_value(distinct); // the other lanes have not counted

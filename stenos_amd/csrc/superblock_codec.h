@@ -22,6 +22,11 @@ inline uint64_t& emul_group4_packed_count() // (groups whose second pass took th
 	static uint64_t n = 0;
 	return n;
 }
+inline uint64_t& emul_group4_expected_count() // (groups whose blocks were scanned against the planes the wave expected, and accepted)
+{
+	static uint64_t n = 0;
+	return n;
+}
 inline uint64_t& emul_group_any_count()
 {
 	static uint64_t n = 0;
@@ -198,7 +203,11 @@ struct StreamSink { // a contiguous stream in HBM (RunStream)
 	uint8_t* raw_to = nullptr;
 	// Whether the last blocks the wave saw had the shape that groups of four want (encode_blocks_to): kept by the caller from
 	// run to run, so that a run of noise does not begin with four loads for nothing.  nullptr: every run tries once.
-	bool* group_hint = nullptr;
+	// 0: they had not.  GROUP_TRY: they had (or nothing is known).  Any other value: they had, and these were the two planes that
+	// varied in the last group (slot_codec.h, plane_bytes: 0xFF in two bytes, so never 0 or GROUP_TRY): the next group's blocks are
+	// scanned against them.
+	static constexpr uint32_t GROUP_TRY = 1;
+	uint32_t* group_hint = nullptr;
 	WV_MFN void raw8(const RawBlock8& b, uint32_t block)
 	{
 		gst128_through(raw_to + (uint64_t)block * 2048u, lane_id() * 32u, b.a);
@@ -299,7 +308,11 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 		// Four blocks with the same two planes that are not constant, taken plane by plane (slot_codec.h, "groups of four
 		// blocks").  False: the blocks are not of that shape, or one of them may go to the mini-LZ -- nothing has been written,
 		// the pass below takes them.  try_group: the last blocks seen had the shape (or nothing is known yet).
-		bool try_group = sink.group_hint ? *sink.group_hint : true;
+		const uint32_t hint_in = sink.group_hint ? *sink.group_hint : StreamSink::GROUP_TRY;
+		bool try_group = hint_in != 0;
+		// The two planes that varied in the wave's last group, as plane_bytes has them (0: none yet).  Like try_group it only selects
+		// which tests run: the scan against an expectation accepts exactly what the four general scans accept.
+		uint32_t want = hint_in > StreamSink::GROUP_TRY ? hint_in : 0u;
 		RawProofHint proof0, proof1; // (the first and the second pass of a group; the passes below use the first)
 		auto group4 = [&]() __attribute__((always_inline)) -> bool {
 			const uint8_t* a = src + (uint64_t)i * bs;
@@ -307,25 +320,43 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 			const RawBlock e0 = Src::raw_block(a, T), e1 = Src::raw_block(a + bs, T), e2 = Src::raw_block(a + 2 * bs, T), e3 = Src::raw_block(a + 3 * bs, T);
 			const Layout M = sink.at(L);
 			WV_MARK("g4_front");
-			const SameScan s0 = scan_same_fast(e0, T);
-			if (s0.nact != 2) {
-				try_group = false;
-				return false;
+			bool expected = false;
+			// (said to be the same in every lane, here and below: the compiler takes what the loop carries and what the scans return for
+			// divergent, and a branch on such a value is laid out around lane masks)
+			want = first_lane_value(want);
+			if (T == 4 && want) {
+				WV_NESTED();
+				expected = scan_expected_group4(e0.e, e1.e, e2.e, e3.e, want);
 			}
-			const SameScan s1 = scan_same_fast(e1, T), s2 = scan_same_fast(e2, T), s3 = scan_same_fast(e3, T);
-			if (s1.act != s0.act || s2.act != s0.act || s3.act != s0.act) {
-				try_group = false;
-				return false;
+			if (!expected) { // no expectation, or the blocks differ from it: the general scan decides
+				const SameScan s0 = scan_same_fast(e0, T);
+				if (s0.nact != 2) {
+					try_group = false;
+					return false;
+				}
+				const SameScan s1 = scan_same_fast(e1, T), s2 = scan_same_fast(e2, T), s3 = scan_same_fast(e3, T);
+				if (s1.act != s0.act || s2.act != s0.act || s3.act != s0.act) {
+					try_group = false;
+					return false;
+				}
+				want = first_lane_value(plane_bytes(s0.act));
 			}
-			const uint32_t k0 = (uint32_t)__builtin_ctz(s0.act), k1 = 31u - (uint32_t)__builtin_clz(s0.act);
+#ifdef WV_HOST_EMULATION
+			else
+				++emul_group4_expected_count();
+#endif
+			const uint32_t k0 = (uint32_t)__builtin_ctz(want) >> 3, k1 = (31u - (uint32_t)__builtin_clz(want)) >> 3;
 			// (first rejection test of the mini-LZ, as in the pass below; the counts of the four blocks, a byte each)
 			const uint32_t keys = T == 4 ? lz_distinct_keys_group4(lds, M, e0.e, e1.e, e2.e, e3.e) : 0u;
-			const uint32_t keys0 = keys & 0xFFu, keys1 = (keys >> 8) & 0xFFu, keys2 = (keys >> 16) & 0xFFu, keys3 = keys >> 24;
 			// plane k0 of block q -> slot q, plane k1 -> slot 4 + q
-			write_slots_fast(lds, M, e0, T, s0.act, 0, 4);
-			write_slots_fast(lds, M, e1, T, s0.act, 1, 4);
-			write_slots_fast(lds, M, e2, T, s0.act, 2, 4);
-			write_slots_fast(lds, M, e3, T, s0.act, 3, 4);
+			if (T == 4)
+				write_slots_group4(lds, M, e0.e, e1.e, e2.e, e3.e, k0, k1);
+			else {
+				write_slots_fast(lds, M, e0, T, 3u, 0, 4);
+				write_slots_fast(lds, M, e1, T, 3u, 1, 4);
+				write_slots_fast(lds, M, e2, T, 3u, 2, 4);
+				write_slots_fast(lds, M, e3, T, 3u, 3, 4);
+			}
 			// an element of its block for the sixteen lanes of each block (the bytes of the constant planes)
 			const U32 firstv = T == 4 ? row_select4v(e0.e.x, e1.e.x, e2.e.x, e3.e.x) : U32(0u);
 			if (sink.raw_to) { // (measured only, probably a copy: the raw bytes go where the copy would put them)
@@ -354,10 +385,10 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 			incl = incl + scan_source(incl, 5, 0u);
 			const uint32_t total = readlane(incl, 63);
 			if (T == 4) {
-				// a block the mini-LZ may take (block_compress.h:1210-1221): the pass below decides and encodes it
-				const uint32_t f0 = readlane(bsz, 0) - hs, f1 = readlane(bsz, 16) - hs, f2 = readlane(bsz, 32) - hs, f3 = readlane(bsz, 48) - hs;
-				if ((f0 * 3 > bs && lz_precheck_passes(T, keys0, f0)) || (f1 * 3 > bs && lz_precheck_passes(T, keys1, f1)) ||
-				    (f2 * 3 > bs && lz_precheck_passes(T, keys2, f2)) || (f3 * 3 > bs && lz_precheck_passes(T, keys3, f3))) {
+				// a block the mini-LZ may take (block_compress.h:1210-1221): the pass below decides and encodes it.  Every lane holds
+				// the size of its block and takes its block's byte of the key counts: the test of the four blocks is one test in lanes.
+				const U32 f = bsz - U32(hs), d = bfe(U32(keys), (lane_id() >> 1) & 24u, U32(8u));
+				if (any((f * U32(3u) > U32(bs)) & lz_precheck_passes_lanes(T, d, f))) {
 					try_group = false; // (the groups of any shape look at such blocks again; then the pass)
 					return false;
 				}
@@ -748,7 +779,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 		if (i < nblocks)
 			pass(std::false_type());
 		if (sink.group_hint)
-			*sink.group_hint = try_group;
+			*sink.group_hint = try_group ? (want ? want : StreamSink::GROUP_TRY) : 0u;
 		return;
 	}
 	if (slots && T == 8) {
@@ -849,7 +880,7 @@ WV_FN void encode_blocks_to(Sink& sink, Lds lds, const Layout& L, uint32_t T, co
 // raw_to (only without a stage): the blocks' raw bytes are stored there on the way (StreamSink::raw_to)
 template <class Hook = NoPassHook, class Src = PlainSource>
 WV_FN uint32_t encode_run(Lds lds, const Layout& L, uint32_t T, const uint8_t* src, uint32_t nblocks, uint8_t* stage, bool slots = true, Hook hook = Hook(),
-			  uint8_t* raw_to = nullptr, bool* group_hint = nullptr)
+			  uint8_t* raw_to = nullptr, uint32_t* group_hint = nullptr)
 {
 	StreamSink sink;
 	sink.group_hint = group_hint;
