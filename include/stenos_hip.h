@@ -153,6 +153,71 @@ STENOS_EXPORT size_t stenos_hip_decompress_ranges(stenos_context* ctx, const voi
 STENOS_EXPORT size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t row_bytes, size_t n,
 					    const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream);
 
+/* Gather of VARIABLE-LENGTH ranges: n byte ranges of the ORIGINAL array out of one frame in device memory, by offsets and lengths
+ * that live in DEVICE memory -- the device-resident form of stenos_hip_decompress_ranges, with a packed, CSR-style output.
+ * d_offsets and d_lengths have n entries each; bytes [d_offsets[i], d_offsets[i] + d_lengths[i]) go to d_dst + D[i], where D is the
+ * exclusive prefix sum of the lengths.  d_dst_offsets may be NULL; where it is not, it receives the n + 1 entries of D, D[n] being
+ * the total: what the caller indexes the packed output with.  It must not overlap d_dst, d_offsets or d_lengths (the offsets and
+ * lengths are read again after D has been written: in place is not supported).  The host never reads d_offsets or
+ * d_lengths on the common path, and every enqueued step is ordered on `stream`: offsets written by earlier work on that stream (a
+ * kernel, a torch op) need no synchronisation by the caller.  Any offset and any length; length 0 is allowed (it delivers nothing
+ * and makes no piece); ranges may overlap and repeat, in any order; d_dst may have any alignment.  Returns D[n], or an error code
+ * for the call as a whole; n == 0 returns 0 before the devices are looked at.  Waits for completion (there is no _async form).
+ * dst_size is the REAL capacity of d_dst in bytes, not a "large enough" constant: it sizes the call's tables and grids (below).
+ * On success nothing outside [d_dst, d_dst + D[n]) is written.  On a host-side refusal, an invalid range or an overflow (all
+ * below) NO BYTE of d_dst is written.  After a decode error d_dst may be partly written, inside [d_dst, d_dst + D[n]).  What
+ * d_dst_offsets holds after an error is unspecified.
+ * Refused on the host, before any launch:
+ *   STENOS_ERROR_INVALID_INSTRUCTION_SET  no usable device;
+ *   STENOS_ERROR_INVALID_PARAMETER        bytesoftype outside 1..64, a piece bound (below) or the decode grid for it above
+ *                                         2^31 - 1, or while an _async job on ctx is unfinished (that job is left alone);
+ *   a frame header stenos_hip_decompress refuses: its error code.
+ * The frame of an EMPTY array is accepted: only ranges of length 0 at offset 0 are valid in it.  It has no superblock and so no
+ * piece: its Pmax is 0 whatever dst_size is, no table or grid is sized by dst_size and no dst_size is refused.
+ * RANGES ARE CHECKED ON THE DEVICE: a valid range has offset <= array size and length <= array size - offset (no sum that may
+ * wrap is formed).  Any invalid range gives STENOS_ERROR_INVALID_PARAMETER; otherwise D[n] > dst_size gives
+ * STENOS_ERROR_DST_OVERFLOW.  Both come in front of any decode error and both leave d_dst untouched: the stage that forms D leaves
+ * a status bit, with such a bit set no piece is made and every decoding wavefront leaves at its first test.  No extra host round
+ * trip is spent on this.
+ * d_index is as for stenos_hip_gather_rows: NULL has the chain walked first (into the context's own index); an index that is
+ * given is used as it is.  It may be the context's own, from stenos_hip_frame_index / stenos_hip_last_index: this call leaves
+ * that buffer intact (its tables live in a buffer of their own), any number of calls.
+ * HOW: the pieces of a range are its intersections with the superblocks it touches, in order: non-empty, disjoint, their lengths
+ * sum to the length.  One thread per range tests it and counts its bytes and pieces; three passes ordered by the stream (sums per
+ * block of 256 ranges, one workgroup over the sums, apply -- no workgroup waits for another) form D and the first piece slot of
+ * every range; one thread per piece slot finds its range by binary search and cuts its piece, so a long range is not serial
+ * work; the pieces are grouped by superblock, and stenos_hip_gather_rows's decoder, unchanged, walks a superblock's chain of
+ * blocks once for up to 64 of its pieces, up to the block that holds the last byte any of them asks for.  A range of length
+ * L >= 1 touches at most floor((L - 1) / superblock size) + 2 superblocks, so a call that fits dst_size has at most
+ *   Pmax = 2 n + floor(dst_size / superblock size)
+ * pieces: Pmax sizes the piece table and the grids; threads and wavefronts beyond the real counts leave at once.  Host round trips:
+ * the frame header, then the status together with D[n].  Launches and round trips depend neither on n, nor on the lengths, nor
+ * on the number of superblocks.  A piece that is a whole superblock takes the same path through the wavefront's LDS image: a
+ * caller with ranges of a superblock or more is better served by stenos_hip_decompress_ranges.
+ * DEVICE MEMORY the context keeps for this call (it grows to the largest call and is freed with the context): 16 bytes per
+ * bounded piece (16 Pmax); per range 4 bytes (its first piece slot), 8 more where d_dst_offsets is NULL (D), and 12 bytes per
+ * 256 ranges (the blocks' sums); per superblock of the frame 16 bytes (counts, flags, two prefix tables); 64 bytes of words.
+ * WHO IS SERVED BY WHAT (MI355X, int32, level 1, 1 GiB frame, index passed in, medians of 20 after 3 untimed rounds; tools/gather_ranges_rate.py,
+ * profiles/gather_ranges_rate.txt; the other side is the only way without this call: offsets and lengths to the
+ * host, destination addresses formed there, one stenos_hip_decompress_ranges):
+ * Many short ranges are what this call is for.  It WINS: 65 536 ranges of 1..8 KiB at uniform random offsets take 0.55 ms (485 GB/s
+ * delivered, 2.4 MiB of device memory held) against 1.91 ms, x3.5; 2^20 ranges of 1..512 B take 1.16 ms (36 MiB held) against
+ * 26.1 ms, x22; 65 536 ranges of exactly 4 KiB take 0.53 ms against 1.85 ms, x3.5 -- and 0.52 ms through stenos_hip_gather_rows,
+ * so raggedness itself (the measuring, the scan and the binary search per piece) costs under 3 % there.  It LOSES with a few long
+ * ranges: 16 ranges of 16 MiB take 0.42 ms against 0.34 ms (x0.83; every piece is a whole superblock, which the ranges call
+ * decodes by the path of stenos_hip_decompress).  ONE range of 4 KiB is a tie inside the noise (0.196 against 0.198 ms, the two
+ * series of the other side 6 us apart): seven kernel launches and the larger tables on this side, the copies of offset and length to
+ * the host on the other.
+ * WHAT IS CHECKED: only the superblocks a range touches are read, and of those only the blocks up to the last byte asked
+ * for.  Damage anywhere else in the frame is NOT detected by this call (with d_index == NULL the walk still sees every
+ * superblock header).  A truncated or malformed superblock or block that is decoded gives STENOS_ERROR_SRC_OVERFLOW /
+ * STENOS_ERROR_INVALID_INPUT as in stenos_hip_decompress.
+ * Superblocks with zstd-based codes (every superblock of a level >= 2 frame and of bytesoftype 1, the last superblock under
+ * 128 bytes of a level-1 frame) are finished on the host: d_offsets and d_lengths come down, the host forms D, cuts the pieces
+ * of those superblocks again with the same cutting function and inflates them piece by piece, which is slow. */
+STENOS_EXPORT size_t stenos_hip_gather_ranges(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t n, const uint64_t* d_offsets,
+					      const uint64_t* d_lengths, void* d_dst, size_t dst_size, uint64_t* d_dst_offsets, const uint64_t* d_index, void* stream);
+
 /* Gather from MANY frames in one call: n rows, each out of one of m frames in device memory, by (frame number, row number)
  * pairs that live in DEVICE memory.  d_frames and sizes are HOST arrays of m: the frames' device pointers and their sizes in
  * bytes.  Slot i, [d_dst + i * dst_stride, + row_bytes), receives row d_rows[i] of the original array of frame d_frame_ids[i];

@@ -94,6 +94,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "stenos_hip_decompress_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_decompress_ranges": (sz, [vp, vp, sz, sz, sz, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64), ctypes.POINTER(vp), vp, vp]),
         "stenos_hip_gather_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp]),
+        "stenos_hip_gather_ranges": (sz, [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]),
         "stenos_hip_gather_rows_batch": (sz, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, sz, vp, vp, vp, sz, vp, vp]),
         "stenos_hip_frames_index": (vp, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(sz), vp]),
         "stenos_hip_update_rows": (sz, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, vp]),
@@ -258,6 +259,37 @@ class Stenos:
         dst = out if isinstance(out, int) else out.data_ptr()
         return self._check(self.lib.stenos_hip_gather_rows(self.ctx, frame.data_ptr(), bytesoftype, csize, row_bytes, rows.numel(), rows.data_ptr(), dst, stride, index_ptr,
                                                            self._stream_ptr()))
+
+    def gather_ranges(self, frame, bytesoftype: int, csize: int, offsets, lengths, out, out_offsets=None, index_ptr: int | None = None,
+                      out_size: int | None = None) -> int:
+        """Bytes [offsets[i], offsets[i] + lengths[i]) of the ORIGINAL array out of frame[:csize], packed back to back into out:
+        range i begins at D[i], the exclusive prefix sum of the lengths.  offsets, lengths: contiguous int64 or uint64 CUDA
+        tensors of equal length n (they stay on the device and may have been written by earlier work on the current stream; a
+        negative int64 is a huge unsigned value and therefore invalid).  out: a uint8 CUDA tensor, or a raw device address
+        together with out_size; out_size (the real capacity, it sizes the call's tables) defaults to out.numel().  out_offsets:
+        an optional int64 or uint64 CUDA tensor of n + 1 that receives D, D[n] being the total.  index_ptr: as for gather_rows.
+        Returns the bytes delivered; an invalid range raises STENOS_ERROR_INVALID_PARAMETER, lengths that sum to more than
+        out_size raise STENOS_ERROR_DST_OVERFLOW, both with out untouched."""
+        import torch
+
+        for t, name in ((offsets, "offsets"), (lengths, "lengths")):
+            if not t.is_cuda or t.dtype not in (torch.int64, torch.uint64) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int64 or uint64 CUDA tensor")
+        n = offsets.numel()
+        if lengths.numel() != n:
+            raise ValueError("offsets and lengths must have the same length")
+        if out_offsets is not None and (not out_offsets.is_cuda or out_offsets.dtype not in (torch.int64, torch.uint64) or not out_offsets.is_contiguous()
+                                        or out_offsets.numel() != n + 1):
+            raise ValueError("out_offsets must be a contiguous int64 or uint64 CUDA tensor of n + 1")
+        if isinstance(out, int):
+            if out_size is None:
+                raise ValueError("a raw address needs out_size")
+            dst = out
+        else:
+            dst = out.data_ptr()
+            out_size = out.numel() if out_size is None else out_size
+        return self._check(self.lib.stenos_hip_gather_ranges(self.ctx, frame.data_ptr(), bytesoftype, csize, n, offsets.data_ptr(), lengths.data_ptr(), dst, out_size,
+                                                             None if out_offsets is None else out_offsets.data_ptr(), index_ptr, self._stream_ptr()))
 
     def frames_index(self, frames, bytesoftype: int, csizes):
         """The superblock header offsets of all `frames` (frames[f][:csizes[f]]) in one device array, as gather_rows_batch takes

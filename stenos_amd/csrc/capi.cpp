@@ -469,6 +469,20 @@ size_t stenos_hip_gather_rows(stenos_context* ctx, const void* d_src, size_t byt
 		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
 	return gather_rows(ctx, d_src, bytesoftype, bytes, row_bytes, n, d_rows, d_dst, dst_stride, d_index, (hipStream_t)stream);
 }
+size_t stenos_hip_gather_ranges(stenos_context* ctx, const void* d_src, size_t bytesoftype, size_t bytes, size_t n, const uint64_t* d_offsets, const uint64_t* d_lengths,
+				void* d_dst, size_t dst_size, uint64_t* d_dst_offsets, const uint64_t* d_index, void* stream)
+{
+	if (n == 0)
+		return 0;
+	if (!ctx || !d_src || !d_offsets || !d_lengths || (!d_dst && dst_size))
+		return STENOS_ERROR_INVALID_PARAMETER;
+	// what needs no device to be refused: the bytesoftype, and so many ranges that two pieces each pass 2^31 - 1
+	if (bytesoftype == 0 || bytesoftype > STENOS_K_LDS_MAX_T || n > 0x7FFFFFFFull / 2)
+		return STENOS_ERROR_INVALID_PARAMETER;
+	if (!ctx->device_ready())
+		return STENOS_ERROR_INVALID_INSTRUCTION_SET;
+	return gather_ranges(ctx, d_src, bytesoftype, bytes, n, d_offsets, d_lengths, d_dst, dst_size, d_dst_offsets, d_index, (hipStream_t)stream);
+}
 size_t stenos_hip_gather_rows_batch(stenos_context* ctx, size_t m, size_t bytesoftype, const void* const* d_frames, const size_t* sizes, size_t row_bytes, size_t n,
 				    const uint64_t* d_frame_ids, const uint64_t* d_rows, void* d_dst, size_t dst_stride, const uint64_t* d_index, void* stream)
 {

@@ -56,6 +56,8 @@ inline size_t status_error(uint32_t status)
 {
 	if (status & DECODE_STATUS_BAD_ROW)
 		return STENOS_ERROR_INVALID_PARAMETER;
+	if (status & DECODE_STATUS_DST_OVERFLOW)
+		return STENOS_ERROR_DST_OVERFLOW;
 	if (status & DECODE_STATUS_TRUNCATED)
 		return STENOS_ERROR_SRC_OVERFLOW;
 	if (status & DECODE_STATUS_INVALID)

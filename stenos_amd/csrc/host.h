@@ -1,6 +1,6 @@
 // host.h -- internal to the host side of libstenos.so (never installed): the types the units share, the framing helpers
 // and the prototypes they call across.  One unit per concern: host_support.cpp (zstd loader, worker threads),
-// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, append_host.cpp, append_batch_host.cpp, host_pointer.cpp and
+// encode_host.cpp (levels 0/1), strategy_host.cpp (levels >= 2), decode_host.cpp, batch_host.cpp, range_host.cpp, gather_host.cpp, gather_ranges_host.cpp, gather_batch_host.cpp, update_host.cpp, update_batch_host.cpp, append_host.cpp, append_batch_host.cpp, host_pointer.cpp and
 // capi.cpp (the exported functions); frame_access.h is the front end of those that read a frame in device memory.  Everything here
 // is hidden from the library's users (libstenos.map).
 #pragma once
@@ -271,6 +271,7 @@ struct stenos_context_s {
 	DevBuf btab;                                     // batch calls: item tables and per-item words (stenos_hip_compress_batch / decompress_batch)
 	DevBuf rtab, rsb;                                // range calls: status word, unit table and per-unit words (stenos_hip_decompress_ranges); one decoded superblock (codes 3, 4)
 	DevBuf gtab;                                     // gather calls: status word, per-superblock counts, flags and prefixes, the piece table (stenos_hip_gather_rows)
+	DevBuf grtab;                                    // gather of ranges: words, per-superblock counts, flags and prefixes, the piece table, per-range starts and the blocks' sums (stenos_hip_gather_ranges)
 	DevBuf gbtab;                                    // batched gather calls: frame tables, walk arguments and the piece tables (stenos_hip_gather_rows_batch, stenos_hip_frames_index)
 	DevBuf utab, uraw, uenc;                         // update calls: words, tables and both indices; the touched superblocks decoded; encoded again (stenos_hip_update_rows)
 	DevBuf ubtab;                                    // batched update calls: frame tables, the piece tables, slots' lists, both indices, the encoder's item tables (stenos_hip_update_rows_batch)
@@ -281,6 +282,7 @@ struct stenos_context_s {
 	HostBuf h_btab;                                  // batch calls: page-locked mirror of btab (tables up, per-item results down)
 	HostBuf h_rtab;                                  // range calls: page-locked mirror of rtab
 	HostBuf h_gtab;                                  // gather calls, zstd-based codes only: the row numbers and the superblock flags on the host
+	HostBuf h_grtab;                                 // gather of ranges: the call's words as they come back (page-locked); zstd-based codes only: offsets, lengths and the superblock flags
 	HostBuf h_gbtab;                                 // batched gather calls: page-locked mirror of gbtab's frame tables
 	HostBuf h_utab;                                  // update calls, zstd-based codes only: the list of touched superblocks and the superblock flags on the host
 	HostBuf h_ubtab;                                 // batched update calls: page-locked mirror of ubtab's tables of O(frames)
@@ -350,7 +352,7 @@ struct stenos_context_s {
 	// everything the context owns on a device: buffers, events and streams
 	void release_device_state()
 	{
-		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &gbtab, &utab, &uraw, &uenc, &ubtab, &atab, &araw, &aenc, &abtab, &abraw, &abenc };
+		DevBuf* all[] = { &in, &out, &slots, &bsize, &binfo, &bneed, &boff, &sbcsize, &sbneed, &sbcode, &sboff, &misc, &tmp1, &tmp2, &qprod, &shuf, &mid0, &mid1, &chain, &wide, &walk, &dslots, &dtab, &btab, &rtab, &rsb, &gtab, &grtab, &gbtab, &utab, &uraw, &uenc, &ubtab, &atab, &araw, &aenc, &abtab, &abraw, &abenc };
 		for (DevBuf* b : all)
 			b->release();
 		if (h_total)
@@ -410,7 +412,7 @@ struct stenos_context_s {
 				free(l);
 			}
 		release_device_state();
-		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_gbtab, &h_utab, &h_ubtab, &h_atab, &h_abtab };
+		HostBuf* host[] = { &h_in, &h_out, &h_blocks, &h_shuf, &h_mid0, &h_mid1, &h_stage, &h_tab, &h_btab, &h_rtab, &h_gtab, &h_grtab, &h_gbtab, &h_utab, &h_ubtab, &h_atab, &h_abtab };
 		for (HostBuf* b : host)
 			b->release();
 	}
@@ -494,6 +496,10 @@ size_t decompress_ranges(stenos_context_s* ctx, const void* d_src, size_t T, siz
 // gather_host.cpp
 size_t gather_rows(stenos_context_s* ctx, const void* d_src, size_t T, size_t size, size_t row_bytes, size_t n, const uint64_t* d_rows, void* d_dst,
 		   size_t dst_stride, const uint64_t* d_index, hipStream_t stream);
+
+// gather_ranges_host.cpp
+size_t gather_ranges(stenos_context_s* ctx, const void* d_src, size_t T, size_t size, size_t n, const uint64_t* d_offsets, const uint64_t* d_lengths, void* d_dst,
+		     size_t dst_size, uint64_t* d_dst_offsets, const uint64_t* d_index, hipStream_t stream);
 
 // gather_batch_host.cpp
 size_t gather_rows_batch(stenos_context_s* ctx, size_t m, size_t T, const void* const* d_frames, const size_t* sizes, size_t row_bytes, size_t n,

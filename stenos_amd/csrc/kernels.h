@@ -13,6 +13,7 @@ enum : uint32_t {
 	DECODE_STATUS_INVALID = 2,    // malformed block stream or unknown code -> STENOS_ERROR_INVALID_INPUT
 	DECODE_STATUS_HOST_CODES = 4, // superblocks with zstd-based codes 2..5 are present (finished by the host)
 	DECODE_STATUS_BAD_ROW = 8,    // stenos_hip_gather_rows: a row number beyond the array (gather.h) -> STENOS_ERROR_INVALID_PARAMETER
+	DECODE_STATUS_DST_OVERFLOW = 16, // stenos_hip_gather_ranges: the lengths sum to more than dst_size (gather_ranges.h) -> STENOS_ERROR_DST_OVERFLOW
 };
 
 struct DecodeArgs {
